@@ -3,6 +3,12 @@
 config 3: 65,536 mixed spend/output proofs), on N MI355X, one process per GPU.
 
   python bench.py [--gpus N --steps K --warmup W]        (N > 1 under torch.distributed.run)
+  python bench.py --full ...          also the side measurements (roofline passes, other configs, CPU baselines)
+  python bench.py --dump-outputs DIR  also write the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the one JSON result line (the headline, the
+timed region's own phase and host records); everything else the line can report is measured after the
+timed region and only with --full.
 
 A step = one batch verification of the whole 65,536-proof workload: every rank verifies its
 contiguous shard (decode + subgroup checks + batch algebra + per-proof Miller loops + product
@@ -292,11 +298,33 @@ def lineprod_parts(m, ncu, ncoeff=68, pmax=8):
     return b + [ncoeff]
 
 
+def dump_outputs(outdir, result, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files: `verdict` (1.0: the
+    batch's one final exponentiation accepted it) and `statuses` (this rank's per-proof status codes, shard
+    order; 256 KiB for the 65,536-proof batch). The inputs are the same in every run (fixture proofs
+    re-randomized with a fixed seed), and so are these outputs. The 576-byte Miller partial is left out: it
+    depends on the batch scalars the timed path draws from the OS RNG, so it differs from run to run by design.
+    At world > 1 every rank writes its own shard's files with a _rankR suffix."""
+    import numpy as np
+    ok, sts = result
+    os.makedirs(outdir, exist_ok=True)
+    tag = "_rank%d" % rank if world > 1 else ""
+    np.save(os.path.join(outdir, "verdict%s.npy" % tag), np.array([1.0 if ok else 0.0], dtype=np.float32))
+    np.save(os.path.join(outdir, "statuses%s.npy" % tag), np.array(sts, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (the v_mad_u64_u32 peak probe, the "
+                         "isolated-launch roofline pass, the H2D copies, configs 2/4/5, the note-commitment trees, "
+                         "PGHR13, the CPU baselines; --no-iso / --no-configs / --no-cpu leave parts of them out) "
+                         "and report them in the result line; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32)")
     ap.add_argument("--proofs", "--n", dest="n", type=int, default=65536, help="total proofs per step (all ranks)")
     ap.add_argument("--inflight", type=int, default=0,
                     help="batches in flight per GPU, one context each (0: the default, 6)")
@@ -324,13 +352,17 @@ def main():
     ap.add_argument("--rccl-priority", choices=["high", "normal"], default="high",
                     help="RCCL's stream priority (the checkers keep theirs unless --no-priority)")
     ap.add_argument("--dist", action="store_true", help="use torch.distributed (RCCL) even at world size 1")
-    ap.add_argument("--no-iso", action="store_true", help="skip the isolated-launch pass (profiling the timed launches)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the config 2 / config 4 side measurements")
+    ap.add_argument("--no-iso", action="store_true",
+                    help="with --full: skip the isolated-launch pass (profiling the timed launches)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the other configs, the note-commitment trees and PGHR13")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0: every CPU this process may use, capped by OMP_NUM_THREADS (the box's share)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -407,7 +439,8 @@ def main():
     t0 = time.perf_counter()
     proofs = ctx.synth_rerandomize(src_proofs, src_kinds, idx, 2 + 1000003 * rank)
     log("rank %d: generated %d re-randomized proofs in %.1f s" % (rank, shard, time.perf_counter() - t0))
-    peak, clock_hz = ctx.bench_mad_rate(with_clock=True)
+    if args.full:   # the roofline's measured peak
+        peak, clock_hz = ctx.bench_mad_rate(with_clock=True)
 
     dev = torch.device("cuda", local)
     d_proofs = torch.frombuffer(bytearray(proofs), dtype=torch.uint8).to(dev)
@@ -516,6 +549,64 @@ def main():
     host_ms = [1e3 * sum(h[i] for h in host) / len(host) for i in range(3)]
     if vtime:   # deferred verdicts: the worker thread's time per batch (overlaps the next batches)
         host_ms[1] = 1e3 * sum(vtime) / len(vtime)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results[-1], rank, world)
+    total = shard * world
+    value = total * args.steps / dt
+    names = list(Context.PHASES)
+    # phases = HIP events around launch groups; decode = k_decode_sqrt + k_decode_points + k_decode_finish
+    avg = [sum(t[i] for t in timings) / len(timings) for i in range(len(names))]
+    # the headline and what the timed region itself recorded; --full adds the side measurements below
+    out = {
+        "metric": "Sapling Groth16 proofs verified/sec (batch 64k) at 1/2/4/8 MI355X",
+        "value": value, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "u32", "data": "synthetic: real mainnet proofs (reference fixtures) "
+        "re-randomized on GPU, all valid",
+        "config": {"workload": "config 3: 65,536 mixed Sapling spend/output Groth16 proofs, contiguous shard per "
+                               "GPU, one final exponentiation per batch; inputs HBM-resident (H2D copies excluded, "
+                               "see h2d_ms_per_batch of a --full run)",
+                   "collective": ("RCCL all-gather of the %d ranks' 576-B Miller partials (torch.distributed nccl)"
+                                  % world) if use_dist else
+                                 "none (dp1: the one 576-B partial goes straight to the final exponentiation)",
+                   "global_batch": total, "shard": shard, "parallelism": "dp%d" % world,
+                   "batches_in_flight_per_gpu": len(ctxs), "hw_queues": hwq},
+        "phase_ms": dict(zip(names, avg)),
+        "host_ms_per_batch": {"launch": 1e3 * sum(ltime) / max(1, len(ltime)), "wait_partial": host_ms[0],
+                              "exchange_and_final_exp": host_ms[1], "statuses": host_ms[2],
+                              "process_cpus_busy": cpu_busy,
+                              "verdict": "sync" if args.sync_verdict else
+                              ("deferred (ordered gather thread, one coalescing verdict thread: %.2f batches per "
+                               "gt_check_many launch)" % (sum(vsets) / max(1, len(vsets))) if coalesce else
+                               "deferred (ordered gather thread, %d verdict threads with a checker context each)"
+                               % len(checkers))},
+    }
+    if args.full:
+        out.update(side_measurements(args, ctx, Context, local, dev, shard, value, peak, clock_hz, timings, avg,
+                                     launch, complete, proofs, kinds, inputs, src_proofs, src_kinds,
+                                     single=(rank == 0 and world == 1)))
+    st = {}
+    for c in ctxs:
+        for k, v in c.stats().items():
+            st[k] = st.get(k, 0) + v
+    out["context_stats"] = st
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    for c in ctxs + checkers:
+        c.close()
+    if use_dist:
+        dist.destroy_process_group()
+
+
+def side_measurements(args, ctx, Context, local, dev, shard, value, peak, clock_hz, timings, avg, launch, complete,
+                      proofs, kinds, inputs, src_proofs, src_kinds, single):
+    """--full: everything the result line reports beyond the headline, measured after the timed region
+    (launch / complete: main()'s closures over one context's batch; timings: the timed region's phase
+    records, to which complete() appends; single: one process on one GPU, where the other configs and the
+    CPU baselines run)"""
+    import torch
+    names = list(Context.PHASES)
+    NP = len(names)
     # isolated launches (one batch in flight, after the timed region): the kernels' own roofline
     # (ZG_SERIAL_SIDE: this context runs the side-stream work -- K4 and the root's VK pairs -- on
     # its main stream after the product tree, so the Miller kernels are alone on the device)
@@ -535,12 +626,6 @@ def main():
         ictx.close()
 
     h2d = h2d_copy_ms(proofs, kinds, inputs, dev)
-    total = shard * world
-    value = total * args.steps / dt
-    names = list(Context.PHASES)
-    NP = len(names)
-    # phases = HIP events around launch groups; decode = k_decode_sqrt + k_decode_points + k_decode_finish
-    avg = [sum(t[i] for t in timings) / len(timings) for i in range(NP)]
     # roofline of the dominant single kernel: the f-chain (the R-chain + f-chain launch when the
     # shard runs them fused -- its lines phase is then empty), algorithmic MACs per launch over
     # its mean launch duration (HIP events, timed region; with batches in flight a launch shares
@@ -582,19 +667,6 @@ def main():
                       "k_msm_bucket): entries x (4-B entry + 112-B digit operands of C_i) + segment sums written; "
                       "the phase is VALU-bound (mixed additions), not HBM-bound"}
     out = {
-        "metric": "Sapling Groth16 proofs verified/sec (batch 64k) at 1/2/4/8 MI355X",
-        "value": value, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "u32", "data": "synthetic: real mainnet proofs (reference fixtures) "
-        "re-randomized on GPU, all valid",
-        "config": {"workload": "config 3: 65,536 mixed Sapling spend/output Groth16 proofs, contiguous shard per "
-                               "GPU, one final exponentiation per batch; inputs HBM-resident (H2D copies excluded, "
-                               "see h2d_ms_per_batch)",
-                   "collective": ("RCCL all-gather of the %d ranks' 576-B Miller partials (torch.distributed nccl)"
-                                  % world) if use_dist else
-                                 "none (dp1: the one 576-B partial goes straight to the final exponentiation)",
-                   "global_batch": total, "shard": shard, "parallelism": "dp%d" % world,
-                   "batches_in_flight_per_gpu": len(ctxs), "hw_queues": hwq},
         # headline: the dominant kernel ALONE on the GPU (isolated pass); the in-flight launch
         # shares the device with the other batches' kernels, which stretches its duration
         "roofline": {"bound": "valu-int (v_mad_u64_u32)", "kernel": rk, "achieved": iso_achieved / 1e12,
@@ -615,18 +687,9 @@ def main():
                               "sharing the GPU with the other batches in flight"},
         "k4_msm_bucket_phase": k4,
         "job_roofline_frac": value * W_TOTAL * MACS_PER_FQMUL / peak,
-        "phase_ms": dict(zip(names, avg)),
         "h2d_ms_per_batch": h2d,
-        "host_ms_per_batch": {"launch": 1e3 * sum(ltime) / max(1, len(ltime)), "wait_partial": host_ms[0],
-                              "exchange_and_final_exp": host_ms[1], "statuses": host_ms[2],
-                              "process_cpus_busy": cpu_busy,
-                              "verdict": "sync" if args.sync_verdict else
-                              ("deferred (ordered gather thread, one coalescing verdict thread: %.2f batches per "
-                               "gt_check_many launch)" % (sum(vsets) / max(1, len(vsets))) if coalesce else
-                               "deferred (ordered gather thread, %d verdict threads with a checker context each)"
-                               % len(checkers))},
     }
-    if rank == 0 and world == 1 and not args.no_configs:
+    if single and not args.no_configs:
         out["other_configs"] = other_configs(ctx, src_proofs, src_kinds, 0 if args.no_cpu else cpu_threads(args.cpu_threads))
         # note-commitment tree windows (tools/bench_tree.py), not the headline
         from tools import bench_tree
@@ -659,21 +722,11 @@ def main():
                                       "the per-segment trees and the one final exponentiation per call are not "
                                       "counted), not measured instruction counts"}
         out["pghr13_sprout_proofs"] = pg
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if single and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(proofs, kinds, inputs, args.cpu_seconds, cpu_threads(args.cpu_threads))
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         out["gpu_over_cpu_all_usable_projected"] = value / out["cpu_baseline"]["projected_all_usable_cpus"]["value"]
-    st = {}
-    for c in ctxs:
-        for k, v in c.stats().items():
-            st[k] = st.get(k, 0) + v
-    out["context_stats"] = st
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    for c in ctxs + checkers:
-        c.close()
-    if use_dist:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -15,11 +15,11 @@ if [ -z "$2" ]; then
   tail -1 $O/smoke.log
 fi
 t0=$(date +%s.%N)
-timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -30 $O/bench.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -30 $O/bench.err; exit 1; }
 t1=$(date +%s.%N)
 echo "driver bench wall s: $(python3 -c "print($t1-$t0)")" | tee $O/bench_wall.txt
 cat $O/bench.json
-timeout -k 10 200 python -u bench.py --no-cpu --no-configs --proofs 8192 --inflight 8 > $O/bench_8192_if8.json 2> $O/bench_8192_if8.err || { echo "bench 8192 x8 failed"; tail -30 $O/bench_8192_if8.err; exit 1; }
+timeout -k 10 200 python -u bench.py --full --no-cpu --no-configs --proofs 8192 --inflight 8 > $O/bench_8192_if8.json 2> $O/bench_8192_if8.err || { echo "bench 8192 x8 failed"; tail -30 $O/bench_8192_if8.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench_8192_if8.json')); print('8192 x8 in flight', round(d['ms_per_step'],3), 'ms/batch', round(d['value']), 'proofs/s', d['context_stats'])"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 $R/bench.py --no-cpu --no-configs --no-iso --steps 9 --warmup 0 > $O/prof_bench.json 2> $O/prof_bench.err || { echo "rocprof failed"; tail -30 $O/prof_bench.err; exit 1; }

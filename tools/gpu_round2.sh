@@ -3,5 +3,6 @@
 set -o pipefail
 TAG=${1:-run}
 bash tools/gpu_round.sh $TAG || exit 1
-timeout -k 10 120 python -u bench.py --no-cpu --no-configs --n 8192 > gpurun_out/$TAG/bench_8192.json 2> gpurun_out/$TAG/bench_8192.err || { echo "bench 8192 failed"; exit 1; }
-cat gpurun_out/$TAG/bench_8192.json
+O=$(dirname "$(ls -d */$TAG/bench.json | head -1)")   # the folder gpu_round.sh wrote TAG's results to
+timeout -k 10 120 python -u bench.py --full --no-cpu --no-configs --n 8192 > $O/bench_8192.json 2> $O/bench_8192.err || { echo "bench 8192 failed"; exit 1; }
+cat $O/bench_8192.json
