@@ -238,6 +238,30 @@ int zg_sapling_bvk(zg_ctx* ctx, size_t ntx, const uint32_t* n_spends, const uint
                    const int64_t* value_balance, uint8_t* bvk, uint8_t* status);
 int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* status, uint8_t* xy);
 
+/* ---- JoinSplit signatures on the GPU: Ed25519, batched. Any n; device memory
+ * per call, n = 0 and the argument checks as zg_redjubjub_verify.
+ *   zg_ed25519_verify <- JoinSplitVerification::check verification/src/accept_transaction.rs:649-653
+ *        -> crypto::verify_ed25519 crypto/src/lib.rs:298-305 -> ed25519-dalek 1.0.0-pre.1 over
+ *        curve25519-dalek 1.1.4 and sha2 0.8.0 (Cargo.lock:399,466,1559). pubkey n x 32, sig n x 64
+ *        (R || S), msg n x 32 (the no-input sighash) -> status n, the reference's error class; the
+ *        checks run in this order and the first failing one is the status:
+ *          ZG_ED_PUBLIC_ENCODING     PublicKey::from_bytes fails (CompressedEdwardsY::decompress: the
+ *                                    low 255 bits mod p -- no y < p check --, the even root negated
+ *                                    when bit 255 is set, also for x = 0; small-order keys decode)
+ *          ZG_ED_SIGNATURE_ENCODING  Signature::from_bytes fails: sig[63] & 0xE0 != 0 (S is then used
+ *                                    as the 256-bit integer it encodes: S >= l is accepted)
+ *          ZG_ED_SIGNATURE           compress([S]B + [k](-A)) != the 32 bytes of R, k = SHA-512(R ||
+ *                                    pubkey || msg) mod l; cofactorless; a non-canonical R never verifies
+ *   zg_last_sig_kernel_ms: device time (HIP events on the context stream) of the kernel of the most
+ *        recent zg_ed25519_verify or zg_redjubjub_verify on this context (measurement helper) */
+#define ZG_ED_OK 0
+#define ZG_ED_PUBLIC_ENCODING 1    /* Error::InvalidPublicEncoding */
+#define ZG_ED_SIGNATURE_ENCODING 2 /* Error::InvalidSignatureEncoding */
+#define ZG_ED_SIGNATURE 3          /* Error::InvalidSignature */
+int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
+                      uint8_t* status);
+int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms);
+
 /* ---- note-commitment trees on the GPU. Hashes are H256 byte strings
  * (32 B, storage order). kind ZG_TREE_SPROUT: SproutTreeHash, combine = sha256_compress
  * (crypto/src/lib.rs:188-198); ZG_TREE_SAPLING: SaplingTreeHash, combine = pedersen_hash(left,
@@ -351,7 +375,9 @@ int zg_bench_mad_rate_clock(zg_ctx* ctx, double* macs_per_s, double* clock_hz);
  * exact host comparison (tests/test_gpu_field.py; guards the zg_opaque workaround of DESIGN.md
  * section 4). field 0: Fq a b 2^-384 mod p (48-B LE operands), 1: Fq a^2 2^-384 (b unused, a < 2p),
  * 2: Fq2 (96 B = c0 || c1; a lazy < 2p per coefficient, b canonical), 3: BLS12-381 Fr a b 2^-256 mod r
- * (32 B), 4: BN254 Fq a b 2^-256 mod q (32 B). out has the operands' size. */
+ * (32 B), 4: BN254 Fq a b 2^-256 mod q (32 B), 5: a b mod 2^255 - 19 (the 9 x 29-bit-digit product of
+ * zg_ed25519.h; 32-B LE operands of any value < 2^256, canonical result), 6: (a + b 2^256) mod l, l the
+ * Ed25519 group order (32-B operands of any value, canonical result). out has the operands' size. */
 int zg_debug_field_mul(int device, int field, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 
 #ifdef __cplusplus

@@ -26,7 +26,7 @@ use std::convert::TryInto;
 
 use super::cpu::CpuBackend;
 use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, Item};
-use super::ffi::{ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
+use super::ffi::{ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
                  ZG_PREP_KIND_OUTPUT, ZG_PREP_KIND_SPEND};
 use super::{ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_KIND_SPROUT, ZG_STATUS_OK};
 
@@ -75,6 +75,7 @@ pub struct Tx {
     /// first failing check before the JoinSplit stage (version ... eval)
     pub pre_error: Option<String>,
     pub js_pubkey: Option<[u8; 32]>,
+    /// the caller's Ed25519 JoinSplit signature verdict, used when js_sig is None
     pub js_sig_ok: bool,
     pub joinsplits: Vec<JoinSplit>,
     pub js_nullifier_error: Option<String>,
@@ -88,6 +89,9 @@ pub struct Tx {
     pub sighash: Option<[u8; 32]>,
     pub value_balance: i64,
     pub binding_sig: Option<[u8; 64]>,
+    /// the Ed25519 JoinSplit signature over the same sighash (accept_transaction.rs:649-653): with
+    /// it (and js_pubkey, sighash) the signature is verified on the GPU instead of js_sig_ok
+    pub js_sig: Option<[u8; 64]>,
 }
 
 #[derive(Debug, Clone, PartialEq)]
@@ -108,6 +112,8 @@ pub trait Backend {
     fn redjubjub_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 64], u8)]) -> Result<Vec<bool>, GpuError>;
     /// (status, bvk) per (spend cvs, output cvs, valueBalance)
     fn sapling_bvk(&self, txs: &[(Vec<[u8; 32]>, Vec<[u8; 32]>, i64)]) -> Result<Vec<(u8, [u8; 32])>, GpuError>;
+    /// Ed25519 statuses (ZG_ED_*) for (pubkey, signature, 32-byte message)
+    fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError>;
     /// a window's public-input preparation in one call (zg_prep_batch: kinds ZG_PREP_KIND_*, fields
     /// n x ZG_PREP_FIELD_BYTES) -> Some((inputs n x 288 B, codes ZG_PREP_*)); None: the backend has no
     /// batched form and the window is prepared with the per-description host functions
@@ -128,6 +134,9 @@ impl Backend for GpuVerifier {
     }
     fn sapling_bvk(&self, txs: &[(Vec<[u8; 32]>, Vec<[u8; 32]>, i64)]) -> Result<Vec<(u8, [u8; 32])>, GpuError> {
         GpuVerifier::sapling_bvk(self, txs)
+    }
+    fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        GpuVerifier::ed25519_verify(self, items)
     }
     fn prep_batch(&self, kinds: &[u8], fields: &[u8]) -> Result<Option<(Vec<u8>, Vec<u8>)>, GpuError> {
         Ok(Some(GpuVerifier::prep_batch(self, kinds, fields)?))
@@ -326,14 +335,40 @@ fn sig_verdicts<B: Backend>(v: &B, txs: &[Tx]) -> Result<(Vec<Vec<bool>>, Vec<bo
     Ok((sp, bind))
 }
 
+/// per-tx JoinSplit signature verdict: the backend's for transactions with JoinSplits that carry
+/// js_sig and js_pubkey (ONE zg_ed25519_verify call for the window; any non-zero status is the
+/// reference's JoinSplitSignature error), else the caller's js_sig_ok. js_sig without a sighash is
+/// a caller error.
+fn js_sig_verdicts<B: Backend>(v: &B, txs: &[Tx]) -> Result<Vec<bool>, GpuError> {
+    let mut ok: Vec<bool> = txs.iter().map(|t| t.js_sig_ok).collect();
+    let mut items = Vec::new();
+    let mut at = Vec::new();
+    for (i, tx) in txs.iter().enumerate() {
+        if let (Some(sig), Some(pk), false) = (tx.js_sig, tx.js_pubkey, tx.joinsplits.is_empty()) {
+            let sh = match tx.sighash {
+                Some(h) => h,
+                None => return Err(GpuError { code: -1, message: "a transaction carries js_sig but no sighash".to_string() }),
+            };
+            items.push((pk, sig, sh));
+            at.push(i);
+        }
+    }
+    if !items.is_empty() {
+        for (i, st) in at.into_iter().zip(v.ed25519_verify(&items)?) {
+            ok[i] = st == ZG_ED_OK;
+        }
+    }
+    Ok(ok)
+}
+
 fn tx_error(tx: &Tx, plan: &(Vec<Plan>, Vec<Plan>, Vec<Plan>), status: &[u8], pghr_status: &[u8], sp_ok: &[bool],
-            bind_ok: bool) -> Option<TxError> {
+            bind_ok: bool, js_sig_ok: bool) -> Option<TxError> {
     let (js, sp, out) = plan;
     if let Some(e) = &tx.pre_error {
         return Some(TxError::Caller(e.clone()));
     }
     if !tx.joinsplits.is_empty() {
-        if !tx.js_sig_ok {
+        if !js_sig_ok {
             return Some(TxError::JoinSplitSignature);
         }
         for (i, (d, p)) in tx.joinsplits.iter().zip(js).enumerate() {
@@ -391,8 +426,9 @@ pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxEr
     let status = if items.is_empty() { Vec::new() } else { v.verify(&items)? };
     let pghr_status = if pghr.is_empty() { Vec::new() } else { v.pghr13_verify(&pghr)? };
     let (sp_ok, bind_ok) = sig_verdicts(v, txs)?;
+    let js_ok = js_sig_verdicts(v, txs)?;
     for (idx, (tx, plan)) in txs.iter().zip(&plans).enumerate() {
-        if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx]) {
+        if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx], js_ok[idx]) {
             return Ok(Some((idx, e)));
         }
     }

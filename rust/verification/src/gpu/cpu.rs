@@ -11,6 +11,7 @@
 //!   PGHR13    Pghr13Proof::from_raw + crypto::pghr13_verify (sprout.rs:61-67)
 //!   RedJubjub redjubjub::PublicKey::read + verify (sapling.rs:119-137, 216-244), the binding
 //!             verification key as accept_sapling / accept_sapling_final accumulate it
+//!   Ed25519   crypto::verify_ed25519 (accept_transaction.rs:649-653, crypto/src/lib.rs:298-305)
 //!
 //! Nothing here is the test oracle: these are the reference crates' functions. The statuses use
 //! the same ZG_STATUS_* codes as the GPU, so the re-injection of `collect` is shared.
@@ -24,7 +25,8 @@ use crypto::sapling_crypto::jubjub::{edwards, fs::FsRepr, FixedGenerators, Jubju
 use crypto::sapling_crypto::redjubjub::{self, Signature};
 use crypto::{pghr13_verify, Groth16VerifyingKey, Pghr13Proof, Pghr13VerifyingKey, JUBJUB};
 
-use super::ffi::{ZG_GEN_BINDING, ZG_STATUS_INPUT_NONCANONICAL};
+use super::ffi::{ZG_ED_OK, ZG_ED_PUBLIC_ENCODING, ZG_ED_SIGNATURE, ZG_ED_SIGNATURE_ENCODING, ZG_GEN_BINDING,
+                 ZG_STATUS_INPUT_NONCANONICAL};
 use super::{GpuError, Item, ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_STATUS_DECODE_INVALID, ZG_STATUS_MALFORMED_VK,
             ZG_STATUS_OK, ZG_STATUS_VERIFY_FAILED};
 
@@ -136,6 +138,19 @@ impl<'a> super::collect::Backend for CpuBackend<'a> {
                     FixedGenerators::SpendingKeyGenerator
                 };
                 key.verify(&msg[..], &sig, g, &JUBJUB)
+            })
+            .collect())
+    }
+
+    /// crypto::verify_ed25519 for every (pubkey, signature, sighash), its error as ZG_ED_*
+    fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        Ok(items
+            .par_iter()
+            .map(|(pk, sig, msg)| match ::crypto::verify_ed25519(&msg[..], pk, sig) {
+                Ok(()) => ZG_ED_OK,
+                Err(::crypto::Error::InvalidPublicEncoding) => ZG_ED_PUBLIC_ENCODING,
+                Err(::crypto::Error::InvalidSignatureEncoding) => ZG_ED_SIGNATURE_ENCODING,
+                Err(::crypto::Error::InvalidSignature) => ZG_ED_SIGNATURE,
             })
             .collect())
     }

@@ -57,6 +57,11 @@ pub const ZG_R_BYTES: usize = 16;
 
 pub const ZG_GEN_SPEND_AUTH: u8 = 0;
 pub const ZG_GEN_BINDING: u8 = 1;
+// zg_ed25519_verify statuses: the reference's crypto::Error class of the JoinSplit signature check
+pub const ZG_ED_OK: u8 = 0;
+pub const ZG_ED_PUBLIC_ENCODING: u8 = 1;
+pub const ZG_ED_SIGNATURE_ENCODING: u8 = 2;
+pub const ZG_ED_SIGNATURE: u8 = 3;
 pub const ZG_TREE_SPROUT: c_int = 0;
 pub const ZG_TREE_SAPLING: c_int = 1;
 
@@ -121,6 +126,9 @@ extern "C" {
     pub fn zg_sapling_bvk(ctx: *mut ZgCtx, ntx: usize, n_spends: *const u32, n_outputs: *const u32, cvs: *const u8,
                           value_balance: *const i64, bvk: *mut u8, status: *mut u8) -> c_int;
     pub fn zg_jubjub_decode(ctx: *mut ZgCtx, n: usize, points: *const u8, status: *mut u8, xy: *mut u8) -> c_int;
+    pub fn zg_ed25519_verify(ctx: *mut ZgCtx, n: usize, pubkey: *const u8, sig: *const u8, msg: *const u8,
+                             status: *mut u8) -> c_int;
+    pub fn zg_last_sig_kernel_ms(ctx: *mut ZgCtx, ms: *mut f32) -> c_int;
 
     pub fn zg_pghr13_vk_load_builtin(ctx: *mut ZgCtx) -> c_int;
     pub fn zg_pghr13_vk_load_json(ctx: *mut ZgCtx, json: *const c_char, len: usize) -> c_int;

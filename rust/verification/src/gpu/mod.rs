@@ -169,6 +169,27 @@ impl GpuVerifier {
         Ok(ok.into_iter().map(|b| b == 1).collect())
     }
 
+    /// Ed25519 JoinSplit signatures (accept_transaction.rs:649-653 -> crypto::verify_ed25519,
+    /// crypto/src/lib.rs:298-305): per item (pubkey, signature R || S, the 32-byte sighash) ->
+    /// ZG_ED_* (OK, PUBLIC_ENCODING, SIGNATURE_ENCODING, SIGNATURE: the reference's error class).
+    pub fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let n = items.len();
+        let mut pk = Vec::with_capacity(32 * n);
+        let mut sig = Vec::with_capacity(64 * n);
+        let mut msg = Vec::with_capacity(32 * n);
+        for (p, s, m) in items {
+            pk.extend_from_slice(p);
+            sig.extend_from_slice(s);
+            msg.extend_from_slice(m);
+        }
+        let mut status = vec![0u8; n];
+        check(self.ctx, unsafe {
+            ffi::zg_ed25519_verify(self.ctx, n, pk.as_ptr(), sig.as_ptr(), msg.as_ptr(), status.as_mut_ptr())
+        })?;
+        Ok(status)
+    }
+
     /// PHGR JoinSplit proofs (sprout.rs:61-67): per item the 296-byte proof and its
     /// into_bn_frs inputs (`prep_joinsplit_bn`) -> ZG_STATUS_* (DECODE_INVALID = InvalidEncoding,
     /// VERIFY_FAILED = InvalidPGHRProof). The builtin res/sprout-verifying-key.json is loaded on

@@ -279,6 +279,9 @@ mod tests {
         fn sapling_bvk(&self, txs: &[(Vec<[u8; 32]>, Vec<[u8; 32]>, i64)]) -> Result<Vec<(u8, [u8; 32])>, GpuError> {
             Ok(vec![(0, [0u8; 32]); txs.len()])
         }
+        fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+            Ok(vec![0; items.len()])
+        }
     }
 
     /// block i + 1 on parent i: one transaction with one Groth16 JoinSplit

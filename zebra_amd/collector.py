@@ -17,9 +17,11 @@ reference's:
       per output (cv, cmu, epk, proof), binding signature -> any failure is InvalidSapling;
       then Sapling nullifiers
 
-The checks that are not proofs or Sapling signatures (JoinSplit ed25519 signature, tree
-roots, nullifiers, the transparent checks before the shielded stages) are evaluated by the
-caller exactly as today and handed in as outcomes; the collector prepares every public input of
+The checks that are not proofs or signatures (tree roots, nullifiers, the transparent checks
+before the shielded stages) are evaluated by the caller exactly as today and handed in as
+outcomes; the Ed25519 JoinSplit signature too, unless the transaction carries it (Tx.js_sig):
+then every such signature of the window is verified in ONE zg_ed25519_verify call (SURVEY.md 8(f)
+f5; accept_transaction.rs:649-653 -> crypto::verify_ed25519 crypto/src/lib.rs:298-305); the collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
 verifies all Groth16 proofs of the window in
@@ -78,7 +80,7 @@ class Tx:
     """the shielded-proof view of one transaction, with the caller's non-Groth16 outcomes"""
     pre_error: Optional[str] = None           # first failing check before the JoinSplit stage
     js_pubkey: Optional[bytes] = None
-    js_sig_ok: bool = True
+    js_sig_ok: bool = True                    # caller's Ed25519 verdict, used when js_sig is None
     joinsplits: List[JoinSplit] = field(default_factory=list)
     js_nullifier_error: Optional[str] = None
     spends: List[Spend] = field(default_factory=list)
@@ -90,6 +92,9 @@ class Tx:
     sighash: Optional[bytes] = None
     value_balance: int = 0
     binding_sig: Optional[bytes] = None
+    # the JoinSplit signature on the GPU: the 64-byte Ed25519 signature over the
+    # same sighash, checked against js_pubkey (accept_transaction.rs:649-653)
+    js_sig: Optional[bytes] = None
 
 
 _POOL = None
@@ -271,8 +276,34 @@ def _sig_verdicts(txs, ctx, verify_sigs, sapling_bvk):
     return sp_ok, bind_ok
 
 
-def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=()):
+def _js_sig_verdicts(txs, ctx, verify_js_sigs):
+    """the Ed25519 JoinSplit signature verdict of each transaction: the caller's js_sig_ok, or, for a
+    transaction with JoinSplits that carries js_sig and js_pubkey, the status of the window's ONE
+    zg_ed25519_verify call (any non-zero status is the reference's JoinSplitSignature error:
+    crypto::verify_ed25519 maps every dalek error to Err, accept_transaction.rs:649-653)."""
+    ok = [tx.js_sig_ok for tx in txs]
+    need = [i for i, tx in enumerate(txs)
+            if tx.js_sig is not None and tx.joinsplits and tx.js_pubkey is not None]
+    if not need:
+        return ok
+    if any(txs[i].sighash is None for i in need):
+        raise zg.ZgError(-1, "a transaction carries js_sig but no sighash")
+    if verify_js_sigs is None:
+        if ctx is None:
+            raise zg.ZgError(-1, "transactions carry a JoinSplit signature but no Ed25519 backend was given "
+                                 "(pass ctx= or verify_js_sigs=)")
+        verify_js_sigs = ctx.ed25519_verify
+    sts = verify_js_sigs([bytes(txs[i].js_pubkey) for i in need], [bytes(txs[i].js_sig) for i in need],
+                         [bytes(txs[i].sighash) for i in need])
+    for i, st in zip(need, sts):
+        ok[i] = st == zg.ED_OK
+    return ok
+
+
+def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None):
     """the reference's first error of one transaction, given the proof statuses"""
+    if js_sig_ok is None:
+        js_sig_ok = tx.js_sig_ok
     js_plan, sp_plan, out_plan = plan
     if sp_ok is None:
         sp_ok = [s.sig_ok for s in tx.spends]
@@ -281,7 +312,7 @@ def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=()):
     if tx.pre_error:
         return tx.pre_error
     if tx.joinsplits:
-        if not tx.js_sig_ok:
+        if not js_sig_ok:
             return "JoinSplitSignature"
         for i, (d, (how, v)) in enumerate(zip(tx.joinsplits, js_plan)):
             ok = v if how == "caller" else (pghr_status[v] if how == "pghr" else status[v]) == OK
@@ -323,7 +354,8 @@ def _chunked(verify, cap):
     return run
 
 
-def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None):
+def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
+                 verify_js_sigs=None):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -334,7 +366,10 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     batches. Transactions that carry their sighash get their RedJubjub signatures verified on
     the GPU too (verify_sigs / sapling_bvk default to ctx.redjubjub_verify / ctx.sapling_bvk).
     PHGR JoinSplit proofs go through verify_pghr(proofs, inputs) -> statuses, default
-    ctx.pghr13_verify (ONE zg_pghr13_verify call for the window)."""
+    ctx.pghr13_verify (ONE zg_pghr13_verify call for the window). Transactions that carry their
+    JoinSplit signature (Tx.js_sig, with js_pubkey and sighash) get it verified through
+    verify_js_sigs(pubkeys, sigs, msgs) -> ED_* statuses, default ctx.ed25519_verify (ONE
+    zg_ed25519_verify call for the window); the others keep the caller's js_sig_ok."""
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:
         def verify(proofs, kinds, inputs, n_inputs):
@@ -358,8 +393,9 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
             verify_pghr = ctx.pghr13_verify
         pghr_status = list(verify_pghr([p for p, _ in pghr], [inp for _, inp in pghr]))
     sp_ok, bind_ok = _sig_verdicts(txs, ctx, verify_sigs, sapling_bvk)
+    js_ok = _js_sig_verdicts(txs, ctx, verify_js_sigs)
     for idx, (tx, plan) in enumerate(zip(txs, plans)):
-        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status)
+        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx])
         if err is not None:
             return idx, err
     return None

@@ -103,6 +103,7 @@ struct zg_dev {
   };
   std::vector<VKEntry*> vks;  // prepare_verifying_key once per distinct key per device
   uint32_t* jj_comb = nullptr;  // Jubjub generators' comb tables (zg_jubjub.h), built on first use
+  uint32_t* ed_comb = nullptr;  // the Ed25519 base point's comb table (zg_ed25519.h), built on first use
   zg::MerkleDev* merkle = nullptr;  // Pedersen table + empty roots (zg_merkle.hip), first use
   zg::BnDev* bn = nullptr;          // PGHR13 key, line and comb tables (zg_pghr13.hip), first use
   std::atomic<int> inflight{0};     // contexts on this device with a batch begun and not finished
@@ -213,6 +214,8 @@ struct zg_ctx {
   size_t tree_arena_cap = 0;
   void* bn_arena = nullptr;  // zg_pghr13_verify scratch (grow-only, zg_pghr13.hip)
   size_t bn_arena_cap = 0;
+  hipEvent_t sig_ev[2] = {};  // around the kernel of the last signature call (zg_last_sig_kernel_ms), first use
+  float sig_ms = 0.0f;
 };
 
 static int fail(zg_ctx* c, int code, const std::string& msg) {
@@ -265,6 +268,7 @@ static void dev_release(zg_dev* d) {
     delete e;
   }
   if (d->jj_comb) hipFree(d->jj_comb);
+  if (d->ed_comb) hipFree(d->ed_comb);
   merkle_dev_free(d->merkle);
   bn_dev_free(d->bn);
   g_devs[d->device] = nullptr;
@@ -429,6 +433,8 @@ extern "C" void zg_destroy(zg_ctx* ctx) {
   if (ctx->h_gt) hipHostFree(ctx->h_gt);
   for (int i = 0; i < ZG_NEV; i++)
     if (ctx->ev[i]) hipEventDestroy(ctx->ev[i]);
+  for (hipEvent_t e : ctx->sig_ev)
+    if (e) hipEventDestroy(e);
   set_state(ctx, 0);
   zg_dev* d = ctx->dev;
   delete ctx;
@@ -782,6 +788,9 @@ hipError_t launch_jj_comb(hipStream_t st, uint32_t* table);                     
 hipError_t launch_redjubjub(hipStream_t st, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                             const uint8_t* gen, int n, const uint32_t* comb, uint8_t* ok);
 hipError_t launch_jj_decode(hipStream_t st, const uint8_t* pts, int n, uint8_t* status, uint8_t* xy);
+hipError_t launch_ed_comb(hipStream_t st, uint32_t* table);                                    // zg_ed25519.hip
+hipError_t launch_ed25519(hipStream_t st, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg, int n,
+                          const uint32_t* comb, uint8_t* status);
 hipError_t launch_prep_sapling(hipStream_t st, const uint8_t* kinds, const uint8_t* fields, int n, uint8_t* inputs,
                                uint8_t* codes);
 hipError_t launch_sapling_bvk(hipStream_t st, int ntx, const uint32_t* off, const uint32_t* nspends,
@@ -1526,6 +1535,23 @@ struct DevScratch {
   }
 };
 
+// the two events around a signature call's kernel (created on first use)
+static hipError_t sig_events(zg_ctx* ctx) {
+  for (hipEvent_t& e : ctx->sig_ev)
+    if (!e) {
+      const hipError_t r = hipEventCreate(&e);
+      if (r != hipSuccess) return r;
+    }
+  return hipSuccess;
+}
+
+extern "C" int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *ms = ctx->sig_ms;
+  return ZG_OK;
+}
+
 extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                                    const uint8_t* gen, uint8_t* ok) {
   if (!ctx || (n && (!vk || !sig || !msg || !gen || !ok)) || n > (1u << 30)) return ZG_E_INVAL;
@@ -1546,9 +1572,61 @@ extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, con
   HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dmsg, msg, 64 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dgen, gen, n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
   HIPCHK(launch_redjubjub(ctx->stream, dvk, dsig, dmsg, dgen, (int)n, comb, dok));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
   HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ JoinSplit signatures (zg_ed25519.h)
+#define ZG_ED_COMB_BYTES (sizeof(uint32_t) * 27 * (size_t)(32 * 255))
+static int ed_comb(zg_ctx* ctx, const uint32_t** out) {
+  zg_dev* d = ctx->dev;
+  std::lock_guard<std::mutex> g(d->mu);
+  if (!d->ed_comb) {
+    uint32_t* t = nullptr;
+    HIPCHK(hipMalloc(&t, ZG_ED_COMB_BYTES));
+    hipError_t e = launch_ed_comb(ctx->stream, t);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      hipFree(t);
+      return fail(ctx, ZG_E_HIP, std::string("Ed25519 comb table: ") + hipGetErrorString(e));
+    }
+    d->ed_comb = t;
+  }
+  *out = d->ed_comb;
+  return ZG_OK;
+}
+
+extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
+                                 uint8_t* status) {
+  if (!ctx || (n && (!pubkey || !sig || !msg || !status)) || n > (1u << 30)) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!n) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint32_t* comb = nullptr;
+  int rc = ed_comb(ctx, &comb);
+  if (rc) return rc;
+  DevScratch s;
+  uint8_t *dpk, *dsig, *dmsg, *dst;
+  HIPCHK(s.alloc(&dpk, 32 * n));
+  HIPCHK(s.alloc(&dsig, 64 * n));
+  HIPCHK(s.alloc(&dmsg, 32 * n));
+  HIPCHK(s.alloc(&dst, n));
+  HIPCHK(hipMemcpyAsync(dpk, pubkey, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
+  HIPCHK(launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
   return ZG_OK;
 }
 

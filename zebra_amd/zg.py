@@ -14,6 +14,8 @@ if os.environ.get("ZG_LIB_VARIANT"):
 
 KIND_SPEND, KIND_OUTPUT, KIND_SPROUT = 0, 1, 2
 GEN_SPEND_AUTH, GEN_BINDING = 0, 1   # include/zg.h ZG_GEN_*
+# include/zg.h ZG_ED_*: the reference's error class of an Ed25519 JoinSplit signature check
+ED_OK, ED_PUBLIC_ENCODING, ED_SIGNATURE_ENCODING, ED_SIGNATURE = 0, 1, 2, 3
 TREE_SPROUT, TREE_SAPLING = 0, 1     # include/zg.h ZG_TREE_*
 SPROUT_HEIGHT, SAPLING_HEIGHT = 29, 32   # storage/src/tree_state.rs H29 / H32
 E_TREE_FULL = -7
@@ -76,6 +78,8 @@ def lib():
         L.zg_bench_mad_rate_clock.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         L.zg_chacha20_blocks.argtypes = [vp, u8p, u8p, ctypes.c_uint32, ctypes.c_size_t, u8p]
         L.zg_redjubjub_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p, u8p]
+        L.zg_ed25519_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p]
+        L.zg_last_sig_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.zg_sapling_bvk.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), u8p,
                                      ctypes.POINTER(ctypes.c_int64), u8p, u8p]
         L.zg_jubjub_decode.argtypes = [vp, sz, u8p, u8p, u8p]
@@ -181,7 +185,8 @@ def hsig(random_seed, nf0, nf1, pubkey):
     return out.raw
 
 
-FIELD_BYTES = {0: 48, 1: 48, 2: 96, 3: 32, 4: 32}   # zg_debug_field_mul operand sizes
+# zg_debug_field_mul operand sizes (5: a b mod 2^255 - 19, 6: (a + b 2^256) mod l: plain, canonical results)
+FIELD_BYTES = {0: 48, 1: 48, 2: 96, 3: 32, 4: 32, 5: 32, 6: 32}
 
 
 def debug_field_mul(field, a, b, device=0):
@@ -367,6 +372,25 @@ class Context:
         self._chk(lib().zg_redjubjub_verify(self._p, n, b"".join(map(bytes, vks)), b"".join(map(bytes, sigs)),
                                             b"".join(map(bytes, msgs)), bytes(gens), ok))
         return [b == 1 for b in ok.raw[:n]]
+
+    def ed25519_verify(self, pubkeys, sigs, msgs):
+        """per item: ed25519 PublicKey::from_bytes + Signature::from_bytes + verify over the 32-byte
+        message -> list of ED_* statuses (0 ok, 1 key encoding, 2 signature encoding, 3 signature)"""
+        n = len(pubkeys)
+        assert len(sigs) == len(msgs) == n
+        if not (all(len(x) == 32 for x in pubkeys) and all(len(x) == 64 for x in sigs) and
+                all(len(x) == 32 for x in msgs)):
+            raise ZgError(-1, "ed25519_verify takes 32-byte keys, 64-byte signatures and 32-byte messages")
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._chk(lib().zg_ed25519_verify(self._p, n, b"".join(map(bytes, pubkeys)), b"".join(map(bytes, sigs)),
+                                          b"".join(map(bytes, msgs)), st))
+        return list(st.raw[:n])
+
+    def last_sig_kernel_ms(self):
+        """device time of the kernel of the last ed25519_verify / redjubjub_verify call"""
+        ms = ctypes.c_float(0)
+        self._chk(lib().zg_last_sig_kernel_ms(self._p, ctypes.byref(ms)))
+        return ms.value
 
     def sapling_bvk(self, txs):
         """txs: list of (spend cvs, output cvs, value_balance) -> list of (status, bvk bytes)"""
