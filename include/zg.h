@@ -252,8 +252,9 @@ int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* stat
  *                                    as the 256-bit integer it encodes: S >= l is accepted)
  *          ZG_ED_SIGNATURE           compress([S]B + [k](-A)) != the 32 bytes of R, k = SHA-512(R ||
  *                                    pubkey || msg) mod l; cofactorless; a non-canonical R never verifies
- *   zg_last_sig_kernel_ms: device time (HIP events on the context stream) of the kernel of the most
- *        recent zg_ed25519_verify or zg_redjubjub_verify on this context (measurement helper) */
+ *   zg_last_sig_kernel_ms: device time (HIP events on the context stream) of the kernel(s) of the most
+ *        recent zg_ed25519_verify, zg_redjubjub_verify, zg_equihash_verify or zg_headers_verify on this
+ *        context (measurement helper) */
 #define ZG_ED_OK 0
 #define ZG_ED_PUBLIC_ENCODING 1    /* Error::InvalidPublicEncoding */
 #define ZG_ED_SIGNATURE_ENCODING 2 /* Error::InvalidSignatureEncoding */
@@ -261,6 +262,47 @@ int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* stat
 int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
                       uint8_t* status);
 int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms);
+
+/* ---- block headers on the GPU: the Equihash solution, the block hash and the
+ * proof of work of HeaderVerifier::check (verification/src/verify_header.rs:26-32), batched. Any n
+ * (zg_headers_verify: up to 2^20 headers per call); device memory per call, n = 0 and the argument
+ * checks as zg_ed25519_verify.
+ *   zg_equihash_verify <- verify_equihash_solution (verification/src/equihash.rs:80-172) for the
+ *        instances ZG_EQ_* (personalization "ZcashPoW" || LE32(N) || LE32(K)): (200, 9) on chain, (96, 5)
+ *        the reference's test instance (equihash.rs:320-332), (48, 5) small enough to craft solutions.
+ *        inputs n x input_len (1..252 bytes each), solutions n x 1344 / 68 / 36 -> ok n (1/0); repeated
+ *        optional n (1: some index occurs twice). The verdict is the reference's: distinct_indices
+ *        (equihash.rs:258-274) never resets `j`, so only the FIRST index of a left row is compared with
+ *        the right row's indices, and some solutions with a repeated index are accepted (ok = 1,
+ *        repeated = 1) that the Zcash specification rejects.
+ *   zg_headers_verify <- EquihashSolution::deserialize (chain/src/solution.rs), HeaderEquihashSolution::check
+ *        + HeaderProofOfWork::check (verify_header.rs:48-54,116-124) over n x ZG_HEADER_BYTES serialized
+ *        headers (BlockHeader, chain/src/block_header.rs:12-21; equihash_input = bytes 0..140, :30-40).
+ *        status = the first failing check in the reference's order; hashes optional n x 32 (H256 storage
+ *        order: dhash256 of the 1487 bytes, block_header.rs:64-66); flags optional n: every check
+ *        evaluated on its own, whatever the status (for a MALFORMED header over bytes 143.. as they are).
+ *        max_bits: the network's limit as a compact (consensus.network.max_bits().into()).
+ *   zg_pow_valid <- is_valid_proof_of_work (verification/src/work.rs:21-34) over Compact::to_u256
+ *        (primitives/src/compact.rs:45-66, as written: the word of a size <= 3 compact is shifted before
+ *        the sign test; an Err from either compact gives 0). CPU, no context: the same routine the
+ *        kernel uses. hash in H256 storage order. -> 1/0 (ZG_E_INVAL for a null hash) */
+#define ZG_EQ_200_9 0
+#define ZG_EQ_96_5 1
+#define ZG_EQ_48_5 2
+int zg_equihash_verify(zg_ctx* ctx, int params, size_t n, const uint8_t* inputs, size_t input_len,
+                       const uint8_t* solutions, uint8_t* ok, uint8_t* repeated);
+
+#define ZG_HEADER_BYTES 1487
+#define ZG_HDR_OK 0
+#define ZG_HDR_MALFORMED 1 /* bytes 140..142 != fd 40 05: EquihashSolution::deserialize fails */
+#define ZG_HDR_EQUIHASH 2  /* Error::InvalidEquihashSolution */
+#define ZG_HDR_POW 3       /* Error::Pow */
+#define ZG_HDR_F_EQUIHASH 1
+#define ZG_HDR_F_POW 2
+#define ZG_HDR_F_REPEATED 4
+int zg_headers_verify(zg_ctx* ctx, size_t n, const uint8_t* headers, uint32_t max_bits, uint8_t* status,
+                      uint8_t* hashes, uint8_t* flags);
+int zg_pow_valid(uint32_t max_bits, uint32_t bits, const uint8_t hash[32]);
 
 /* ---- note-commitment trees on the GPU. Hashes are H256 byte strings
  * (32 B, storage order). kind ZG_TREE_SPROUT: SproutTreeHash, combine = sha256_compress

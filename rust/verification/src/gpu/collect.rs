@@ -114,6 +114,9 @@ pub trait Backend {
     fn sapling_bvk(&self, txs: &[(Vec<[u8; 32]>, Vec<[u8; 32]>, i64)]) -> Result<Vec<(u8, [u8; 32])>, GpuError>;
     /// Ed25519 statuses (ZG_ED_*) for (pubkey, signature, 32-byte message)
     fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError>;
+    /// header statuses (ZG_HDR_*: the first failing of deserialize / Equihash / proof of work) for
+    /// serialized 1487-byte headers against the compact `max_bits`
+    fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError>;
     /// a window's public-input preparation in one call (zg_prep_batch: kinds ZG_PREP_KIND_*, fields
     /// n x ZG_PREP_FIELD_BYTES) -> Some((inputs n x 288 B, codes ZG_PREP_*)); None: the backend has no
     /// batched form and the window is prepared with the per-description host functions
@@ -137,6 +140,9 @@ impl Backend for GpuVerifier {
     }
     fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
         GpuVerifier::ed25519_verify(self, items)
+    }
+    fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
+        Ok(GpuVerifier::headers_verify(self, headers, max_bits)?.into_iter().map(|r| r.0).collect())
     }
     fn prep_batch(&self, kinds: &[u8], fields: &[u8]) -> Result<Option<(Vec<u8>, Vec<u8>)>, GpuError> {
         Ok(Some(GpuVerifier::prep_batch(self, kinds, fields)?))

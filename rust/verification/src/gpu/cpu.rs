@@ -12,6 +12,8 @@
 //!   RedJubjub redjubjub::PublicKey::read + verify (sapling.rs:119-137, 216-244), the binding
 //!             verification key as accept_sapling / accept_sapling_final accumulate it
 //!   Ed25519   crypto::verify_ed25519 (accept_transaction.rs:649-653, crypto/src/lib.rs:298-305)
+//!   headers   ser::deserialize::<_, BlockHeader>, equihash::verify_block_equihash_solution and
+//!             work::is_valid_proof_of_work, in HeaderVerifier::check's order (verify_header.rs:26-32)
 //!
 //! Nothing here is the test oracle: these are the reference crates' functions. The statuses use
 //! the same ZG_STATUS_* codes as the GPU, so the re-injection of `collect` is shared.
@@ -25,6 +27,7 @@ use crypto::sapling_crypto::jubjub::{edwards, fs::FsRepr, FixedGenerators, Jubju
 use crypto::sapling_crypto::redjubjub::{self, Signature};
 use crypto::{pghr13_verify, Groth16VerifyingKey, Pghr13Proof, Pghr13VerifyingKey, JUBJUB};
 
+use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_MALFORMED, ZG_HDR_OK, ZG_HDR_POW};
 use super::ffi::{ZG_ED_OK, ZG_ED_PUBLIC_ENCODING, ZG_ED_SIGNATURE, ZG_ED_SIGNATURE_ENCODING, ZG_GEN_BINDING,
                  ZG_STATUS_INPUT_NONCANONICAL};
 use super::{GpuError, Item, ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_STATUS_DECODE_INVALID, ZG_STATUS_MALFORMED_VK,
@@ -151,6 +154,29 @@ impl<'a> super::collect::Backend for CpuBackend<'a> {
                 Err(::crypto::Error::InvalidPublicEncoding) => ZG_ED_PUBLIC_ENCODING,
                 Err(::crypto::Error::InvalidSignatureEncoding) => ZG_ED_SIGNATURE_ENCODING,
                 Err(::crypto::Error::InvalidSignature) => ZG_ED_SIGNATURE,
+            })
+            .collect())
+    }
+
+    /// the reference's own header checks, its error as ZG_HDR_*: the header deserialized
+    /// (chain::BlockHeader), verify_block_equihash_solution((200, 9), ..), then is_valid_proof_of_work
+    /// on dhash256 of the serialized bytes
+    fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
+        Ok(headers
+            .par_iter()
+            .map(|raw| {
+                let header: ::chain::BlockHeader = match ::ser::deserialize(&raw[..]) {
+                    Ok(h) => h,
+                    Err(_) => return ZG_HDR_MALFORMED,
+                };
+                if !::equihash::verify_block_equihash_solution((200, 9), &header) {
+                    return ZG_HDR_EQUIHASH;
+                }
+                let hash = ::crypto::dhash256(&raw[..]);
+                if !::work::is_valid_proof_of_work(max_bits.into(), header.bits, &hash) {
+                    return ZG_HDR_POW;
+                }
+                ZG_HDR_OK
             })
             .collect())
     }

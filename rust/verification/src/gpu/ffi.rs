@@ -62,6 +62,18 @@ pub const ZG_ED_OK: u8 = 0;
 pub const ZG_ED_PUBLIC_ENCODING: u8 = 1;
 pub const ZG_ED_SIGNATURE_ENCODING: u8 = 2;
 pub const ZG_ED_SIGNATURE: u8 = 3;
+// zg_equihash_verify instances, zg_headers_verify statuses (the first failing check) and flags (every check)
+pub const ZG_EQ_200_9: c_int = 0;
+pub const ZG_EQ_96_5: c_int = 1;
+pub const ZG_EQ_48_5: c_int = 2;
+pub const ZG_HEADER_BYTES: usize = 1487;
+pub const ZG_HDR_OK: u8 = 0;
+pub const ZG_HDR_MALFORMED: u8 = 1;
+pub const ZG_HDR_EQUIHASH: u8 = 2;
+pub const ZG_HDR_POW: u8 = 3;
+pub const ZG_HDR_F_EQUIHASH: u8 = 1;
+pub const ZG_HDR_F_POW: u8 = 2;
+pub const ZG_HDR_F_REPEATED: u8 = 4;
 pub const ZG_TREE_SPROUT: c_int = 0;
 pub const ZG_TREE_SAPLING: c_int = 1;
 
@@ -129,6 +141,11 @@ extern "C" {
     pub fn zg_ed25519_verify(ctx: *mut ZgCtx, n: usize, pubkey: *const u8, sig: *const u8, msg: *const u8,
                              status: *mut u8) -> c_int;
     pub fn zg_last_sig_kernel_ms(ctx: *mut ZgCtx, ms: *mut f32) -> c_int;
+    pub fn zg_equihash_verify(ctx: *mut ZgCtx, params: c_int, n: usize, inputs: *const u8, input_len: usize,
+                              solutions: *const u8, ok: *mut u8, repeated: *mut u8) -> c_int;
+    pub fn zg_headers_verify(ctx: *mut ZgCtx, n: usize, headers: *const u8, max_bits: u32, status: *mut u8,
+                             hashes: *mut u8, flags: *mut u8) -> c_int;
+    pub fn zg_pow_valid(max_bits: u32, bits: u32, hash: *const u8) -> c_int;
 
     pub fn zg_pghr13_vk_load_builtin(ctx: *mut ZgCtx) -> c_int;
     pub fn zg_pghr13_vk_load_json(ctx: *mut ZgCtx, json: *const c_char, len: usize) -> c_int;

@@ -190,6 +190,59 @@ impl GpuVerifier {
         Ok(status)
     }
 
+    /// verify_equihash_solution (equihash.rs:80-172) for the instance `params` (ffi::ZG_EQ_*): per item
+    /// (input, solution), inputs of one common length 1..=252 -> (ok, repeated) per item. `ok` is the
+    /// reference's verdict, which accepts some solutions with a repeated index (distinct_indices,
+    /// equihash.rs:258-274, compares only the left row's first index); `repeated` tells them apart.
+    pub fn equihash_verify(&self, params: i32, items: &[(Vec<u8>, Vec<u8>)]) -> Result<(Vec<bool>, Vec<bool>), GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let n = items.len();
+        let ilen = items.first().map(|i| i.0.len()).unwrap_or(1);
+        let slen = match params { 0 => 1344, 1 => 68, 2 => 36, _ => 0 };
+        if slen == 0 || items.iter().any(|i| i.0.len() != ilen || i.1.len() != slen) {
+            return Err(GpuError { code: ffi::ZG_E_INVAL, message: "equihash_verify: item sizes".to_string() });
+        }
+        let mut inputs = Vec::with_capacity(ilen * n);
+        let mut sols = Vec::with_capacity(slen * n);
+        for (i, s) in items {
+            inputs.extend_from_slice(i);
+            sols.extend_from_slice(s);
+        }
+        let mut ok = vec![0u8; n];
+        let mut rep = vec![0u8; n];
+        check(self.ctx, unsafe {
+            ffi::zg_equihash_verify(self.ctx, params, n, inputs.as_ptr(), ilen, sols.as_ptr(), ok.as_mut_ptr(),
+                                    rep.as_mut_ptr())
+        })?;
+        Ok((ok.into_iter().map(|b| b == 1).collect(), rep.into_iter().map(|b| b == 1).collect()))
+    }
+
+    /// HeaderEquihashSolution::check + HeaderProofOfWork::check (verify_header.rs:48-54,116-124) over
+    /// serialized 1487-byte headers in ONE call -> per header (status ZG_HDR_*, block hash in H256
+    /// storage order, flags ZG_HDR_F_*). max_bits: `consensus.network.max_bits().into()` as u32.
+    pub fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<(u8, [u8; 32], u8)>, GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let n = headers.len();
+        if headers.iter().any(|h| h.len() != ffi::ZG_HEADER_BYTES) {
+            return Err(GpuError { code: ffi::ZG_E_INVAL, message: "headers_verify: 1487-byte headers".to_string() });
+        }
+        let flat: Vec<u8> = headers.iter().flat_map(|h| h.iter().cloned()).collect();
+        let mut status = vec![0u8; n];
+        let mut hashes = vec![0u8; 32 * n];
+        let mut flags = vec![0u8; n];
+        check(self.ctx, unsafe {
+            ffi::zg_headers_verify(self.ctx, n, flat.as_ptr(), max_bits, status.as_mut_ptr(), hashes.as_mut_ptr(),
+                                   flags.as_mut_ptr())
+        })?;
+        Ok((0..n)
+            .map(|i| {
+                let mut h = [0u8; 32];
+                h.copy_from_slice(&hashes[32 * i..32 * i + 32]);
+                (status[i], h, flags[i])
+            })
+            .collect())
+    }
+
     /// PHGR JoinSplit proofs (sprout.rs:61-67): per item the 296-byte proof and its
     /// into_bn_frs inputs (`prep_joinsplit_bn`) -> ZG_STATUS_* (DECODE_INVALID = InvalidEncoding,
     /// VERIFY_FAILED = InvalidPGHRProof). The builtin res/sprout-verifying-key.json is loaded on

@@ -14,12 +14,22 @@
 //! only after their window verified, in append order, up to the first failing block, whose
 //! error is returned; the window's later blocks are dropped.
 //!
+//! Headers: a block that returns its 1487 serialized header bytes from
+//! `ImportBlock::header` has the Equihash and proof-of-work steps of HeaderVerifier::check
+//! (verify_header.rs:26-32) deferred as well: the window's headers go through ONE
+//! `Backend::headers_verify` call when the window is verified, before the collector call. Per
+//! block the order is `header_precheck` (the version check, at append) -> InvalidEquihashSolution
+//! -> Pow -> `precheck` (the timestamp and everything after it) -> transactions; a block whose
+//! `precheck` fails at append still has its header verified with the window it flushes, and a
+//! header error outranks its `precheck` error. Without a header nothing changes.
+//!
 //! Contract (as in the Python original): identical storage and first error for a caller that
 //! stops at the first error -- the reference's only caller, zebra/commands/import.rs:20-28,
 //! returns on any Err.
 use std::collections::{HashMap, HashSet, VecDeque};
 
 use super::collect::{verify_block, Backend, Tx, TxError};
+use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_OK, ZG_HDR_POW};
 use super::GpuError;
 
 /// sync/src/blocks_writer.rs:20
@@ -48,6 +58,15 @@ pub trait ImportBlock {
     fn precheck(&self, known: &dyn Fn(&[u8; 32]) -> bool) -> Result<(), String>;
     /// the collector view of the transactions (the caller's non-proof outcomes filled in)
     fn txs(&self) -> &[Tx];
+    /// the 1487 serialized header bytes when the writer is to verify the Equihash solution and the
+    /// proof of work; None: the caller ran HeaderVerifier::check itself, inside `precheck`
+    fn header(&self) -> Option<&[u8]> {
+        None
+    }
+    /// the header checks that precede the Equihash solution (HeaderVersion::check), run at append
+    fn header_precheck(&self, _known: &dyn Fn(&[u8; 32]) -> bool) -> Result<(), String> {
+        Ok(())
+    }
 }
 
 /// storage::Store as the writer uses it
@@ -96,6 +115,21 @@ pub struct DeferredBlocksWriter<'a, S: BlockStore<B>, B: ImportBlock, V: Backend
     window: Vec<B>,
     pending: HashSet<[u8; 32]>,
     window_proofs: usize,
+    max_bits: u32,
+}
+
+/// headers per window: a window of header-carrying blocks is verified at the latest when it holds this many
+pub const WINDOW_HEADERS: usize = 16384;
+
+/// Network::Mainnet.max_bits() (network/src/network.rs:14,47-54) as a compact
+pub const MAINNET_MAX_BITS: u32 = 0x1f07ffff;
+
+fn header_error(status: u8) -> String {
+    match status {
+        ZG_HDR_EQUIHASH => "InvalidEquihashSolution".to_string(),
+        ZG_HDR_POW => "Pow".to_string(),
+        _ => "MalformedHeader".to_string(),
+    }
 }
 
 impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, S, B, V> {
@@ -108,7 +142,13 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
             window: Vec::new(),
             pending: HashSet::new(),
             window_proofs: window_proofs.max(1),
+            max_bits: MAINNET_MAX_BITS,
         }
+    }
+
+    /// the network's proof-of-work limit as a compact (`consensus.network.max_bits().into()`)
+    pub fn set_max_bits(&mut self, max_bits: u32) {
+        self.max_bits = max_bits;
     }
 
     pub fn storage(&self) -> &S {
@@ -136,18 +176,29 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
         let mut queue = vec![block];
         queue.extend(self.orphans.remove_for_parent(h));
         for b in queue {
-            let pre = {
+            let (hpre, pre) = {
                 let known = |x: &[u8; 32]| self.pending.contains(x) || self.storage.contains(x);
-                b.precheck(&known)
+                let hpre = if b.header().is_some() { b.header_precheck(&known) } else { Ok(()) };
+                let pre = if hpre.is_ok() { b.precheck(&known) } else { Ok(()) };
+                (hpre, pre)
             };
-            if let Err(e) = pre {
-                // an earlier block of the window may hold the first error: verify those first
+            if let Err(e) = hpre {
+                // fails before its Equihash solution is looked at: only earlier blocks precede it
                 self.flush()?;
+                return Err(WriterError::Verification(e));
+            }
+            if let Err(e) = pre {
+                // an earlier block of the window may hold the first error: verify those first --
+                // with this block's header, whose Equihash / Pow error comes before `e`
+                let backend = self.backend;
+                self.flush_on(backend, b.header())?;
                 return Err(WriterError::Verification(e));
             }
             self.pending.insert(b.hash());
             self.window.push(b);
-            if self.window.iter().map(|x| n_proofs(x.txs())).sum::<usize>() >= self.window_proofs {
+            if self.window.iter().map(|x| n_proofs(x.txs())).sum::<usize>() >= self.window_proofs
+                || self.window.iter().filter(|x| x.header().is_some()).count() >= WINDOW_HEADERS
+            {
                 self.flush()?;
             }
         }
@@ -157,23 +208,45 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
     /// verify the window, insert its blocks up to the first failing one, return its error
     pub fn flush(&mut self) -> Result<(), WriterError> {
         let backend = self.backend;
-        self.flush_on(backend)
+        self.flush_on(backend, None)
     }
 
     /// after `WriterError::Backend`: verify the window the writer still holds on another backend
     /// (the CPU backend of cpu.rs), with the same insertion and first-error contract as `flush`
     pub fn flush_with<W: Backend>(&mut self, other: &W) -> Result<(), WriterError> {
-        self.flush_on(other)
+        self.flush_on(other, None)
     }
 
-    fn flush_on<W: Backend>(&mut self, backend: &W) -> Result<(), WriterError> {
-        if self.window.is_empty() {
+    /// tail: the header of a block that already failed its precheck and is not part of the window;
+    /// it is verified with the window's headers and its error returned after the window's own
+    fn flush_on<W: Backend>(&mut self, backend: &W, tail: Option<&[u8]>) -> Result<(), WriterError> {
+        if self.window.is_empty() && tail.is_none() {
             return Ok(());
         }
-        // the window's transactions, flattened in block order (one verify_block call)
+        // the headers first, ONE call: the first failing header bounds what else can matter
+        let n_seq = self.window.len() + tail.is_some() as usize;
+        let mut with_header = Vec::new();
+        let mut headers: Vec<Vec<u8>> = Vec::new();
+        for (i, h) in self.window.iter().map(|b| b.header()).chain(tail.map(Some)).enumerate() {
+            if let Some(h) = h {
+                with_header.push(i);
+                headers.push(h.to_vec());
+            }
+        }
+        let mut hfail = n_seq;
+        let mut herr = None;
+        if !headers.is_empty() {
+            let sts = backend.headers_verify(&headers, self.max_bits).map_err(WriterError::Backend)?;
+            if let Some(k) = sts.iter().position(|&s| s != ZG_HDR_OK) {
+                hfail = with_header[k];
+                herr = Some(header_error(sts[k]));
+            }
+        }
+        // the transactions of the blocks before the first failing header, flattened in block order
+        // (one verify_block call)
         let mut owner = Vec::new();
         let mut flat: Vec<&Tx> = Vec::new();
-        for (bi, b) in self.window.iter().enumerate() {
+        for (bi, b) in self.window.iter().enumerate().take(hfail) {
             for (ti, t) in b.txs().iter().enumerate() {
                 flat.push(t);
                 owner.push((bi, ti));
@@ -190,7 +263,11 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
         let blocks = std::mem::take(&mut self.window);
         self.pending.clear();
         let (fail_block, err) = match res {
-            None => (blocks.len(), None),
+            // (every transaction verified belongs to a block before hfail: its error wins)
+            None => match herr {
+                Some(e) => (hfail.min(blocks.len()), Some(e)),
+                None => (blocks.len(), None),
+            },
             Some((idx, e)) => {
                 let (bi, ti) = owner[idx];
                 (bi, Some(format!("transaction {}: {:?}", ti, e)))
@@ -281,6 +358,9 @@ mod tests {
         }
         fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
             Ok(vec![0; items.len()])
+        }
+        fn headers_verify(&self, headers: &[Vec<u8>], _max_bits: u32) -> Result<Vec<u8>, GpuError> {
+            Ok(vec![0; headers.len()])
         }
     }
 

@@ -20,6 +20,16 @@ the sequential writer would never have inserted them.
 Error precedence inside a block is the collector's (accept_transaction.rs:68-84,
 accept_chain.rs:76-81: the lowest failing transaction wins); across blocks the lowest block wins.
 
+Headers: a block that carries its 1487 serialized header bytes
+(`Block.header`) has HeaderVerifier::check's Equihash and proof-of-work steps
+(verification/src/verify_header.rs:26-32) deferred too: the headers of a window go through ONE
+zg_headers_verify call when the window is verified, before the collector call. Per block the
+order is the reference's: `header_precheck` (the version check, evaluated at append) ->
+InvalidEquihashSolution -> Pow -> `precheck` (the timestamp and everything after it) ->
+transactions. A block whose `precheck` fails at append still has its header verified with the
+window it flushes, and a header error outranks its `precheck` error. With `header=None` nothing
+changes.
+
 Contract: the equivalence holds for a caller that stops at the first error, as the reference's
 only caller does (zebra/commands/import.rs:20-28 returns on any Err from append_block). The
 error of a block surfaces when its window is verified -- at that block's append_block or at a
@@ -33,6 +43,10 @@ from collections import OrderedDict
 from . import collector
 
 MAX_ORPHANED_BLOCKS = 1024
+MAINNET_MAX_BITS = 0x1f07ffff   # Network::Mainnet.max_bits() (network/src/network.rs:14,47-54) as a compact
+# zg_headers_verify status -> the reference's error (verification/src/error.rs); a header whose solution
+# does not deserialize never reaches the reference's writer
+HEADER_ERRORS = {1: "MalformedHeader", 2: "InvalidEquihashSolution", 3: "Pow"}
 
 
 class WriterError(Exception):
@@ -59,8 +73,12 @@ class Block:
     outcomes that are not proofs (scripts, tree roots, nullifiers, ...) are set on the collector
     Tx objects by the same caller."""
 
-    def __init__(self, hash, parent, txs, precheck=None):
+    def __init__(self, hash, parent, txs, precheck=None, header=None, header_precheck=None):
+        """header: the 1487 serialized header bytes, or None (the caller ran HeaderVerifier::check itself,
+        inside precheck); header_precheck(writer) -> None | error: the checks that precede the Equihash
+        solution (HeaderVersion::check), run when the block is appended"""
         self.hash, self.parent, self.txs, self.precheck = hash, parent, txs, precheck
+        self.header, self.header_precheck = header, header_precheck
 
     def n_proofs(self):
         return sum(len(t.joinsplits) + len(t.spends) + len(t.outputs) for t in self.txs)
@@ -120,9 +138,12 @@ class DeferredBlocksWriter:
     """The same behaviour with the proofs of a window verified in one batch.
 
     verify_window(txs) -> None | (tx_index, error): the collector over the window's flattened
-    transactions (default: collector.verify_block with `ctx`, i.e. one GPU batch)."""
+    transactions (default: collector.verify_block with `ctx`, i.e. one GPU batch).
+    verify_headers(headers) -> list of HDR_* statuses: the window's headers in one call (default:
+    ctx.headers_verify against the compact `max_bits`, the network's proof-of-work limit)."""
 
-    def __init__(self, storage, ctx=None, verify_window=None, window_proofs=65536):
+    def __init__(self, storage, ctx=None, verify_window=None, window_proofs=65536, verify_headers=None,
+                 max_bits=MAINNET_MAX_BITS, window_headers=16384):
         self.storage = storage
         self.orphans = _OrphanPool()
         self.window = []          # pending blocks in chain order (prechecked, not inserted)
@@ -132,6 +153,14 @@ class DeferredBlocksWriter:
             def verify_window(txs):
                 return collector.verify_block(txs, ctx=ctx)
         self.verify_window = verify_window
+        self.window_headers = window_headers
+        if verify_headers is None:
+            def verify_headers(headers):
+                if ctx is None:
+                    raise RuntimeError("a block carries its header but the writer has neither a context "
+                                       "nor verify_headers")
+                return ctx.headers_verify(headers, max_bits)[0]
+        self.verify_headers = verify_headers
 
     def _known(self, h):
         return h in self.pending or self.storage.contains(h)
@@ -146,24 +175,44 @@ class DeferredBlocksWriter:
                 raise WriterError("TooManyOrphanBlocks")
             return
         for b in [block] + self.orphans.remove_for_parent(block.hash):
+            hpre = b.header_precheck(self) if b.header is not None and b.header_precheck else None
+            if hpre is not None:
+                # fails before its Equihash solution is looked at: only earlier blocks can precede it
+                self.flush()
+                raise WriterError("Verification", hpre)
             pre = b.precheck(self) if b.precheck else None
             if pre is not None:
                 # the block fails before its transactions are accepted; an earlier block of the
-                # window may hold the first error: verify (and accept) those first
-                self.flush()
+                # window may hold the first error: verify (and accept) those first -- with this
+                # block's header, whose Equihash / Pow error comes before `pre`
+                self.flush(_tail=b if b.header is not None else None)
                 raise WriterError("Verification", pre)
             self.window.append(b)
             self.pending.add(b.hash)
-            if sum(x.n_proofs() for x in self.window) >= self.window_proofs:
+            if sum(x.n_proofs() for x in self.window) >= self.window_proofs or \
+                    sum(x.header is not None for x in self.window) >= self.window_headers:
                 self.flush()
 
-    def flush(self):
-        """verify the window, insert its blocks up to the first failing one, raise its error"""
-        if not self.window:
+    def flush(self, _tail=None):
+        """verify the window, insert its blocks up to the first failing one, raise its error.
+        _tail: a block that already failed its precheck and is not part of the window; its header is
+        verified with the window's (a header error of it is raised here, after the window's own)"""
+        if not self.window and _tail is None:
             return
         blocks = self.window
+        # the headers first, ONE call: the first failing header bounds what else can matter
+        seq = blocks + ([_tail] if _tail is not None else [])
+        with_header = [i for i, b in enumerate(seq) if b.header is not None]
+        hfail, herr = len(seq), None
+        if with_header:
+            sts = self.verify_headers([seq[i].header for i in with_header])
+            assert len(sts) == len(with_header)
+            for i, st in zip(with_header, sts):
+                if st != 0:
+                    hfail, herr = i, HEADER_ERRORS[st]
+                    break
         flat, owner = [], []
-        for bi, b in enumerate(blocks):
+        for bi, b in enumerate(blocks[:hfail]):
             for ti, t in enumerate(b.txs):
                 flat.append(t)
                 owner.append((bi, ti))
@@ -177,6 +226,9 @@ class DeferredBlocksWriter:
             idx, e = res
             fail_block, ti = owner[idx]
             err = (ti, e)
+        elif herr is not None:
+            # (every transaction in `flat` belongs to a block before hfail: a transaction error wins)
+            fail_block, err = min(hfail, len(blocks)), herr
         for b in blocks[:fail_block]:
             self.storage.insert(b)
         if err is not None:

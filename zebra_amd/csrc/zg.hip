@@ -791,6 +791,11 @@ hipError_t launch_jj_decode(hipStream_t st, const uint8_t* pts, int n, uint8_t* 
 hipError_t launch_ed_comb(hipStream_t st, uint32_t* table);                                    // zg_ed25519.hip
 hipError_t launch_ed25519(hipStream_t st, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg, int n,
                           const uint32_t* comb, uint8_t* status);
+int equihash_solution_bytes(int params);                                                      // zg_equihash.hip
+hipError_t launch_equihash(hipStream_t st, int params, const uint8_t* inputs, size_t in_stride, int in_len,
+                           const uint8_t* sols, size_t sol_stride, int n, uint8_t* ok, uint8_t* repeated);
+hipError_t launch_headers(hipStream_t st, const uint8_t* headers, int n, uint32_t max_bits, uint8_t* eq_ok,
+                          uint8_t* eq_rep, uint8_t* status, uint8_t* hashes, uint8_t* flags);
 hipError_t launch_prep_sapling(hipStream_t st, const uint8_t* kinds, const uint8_t* fields, int n, uint8_t* inputs,
                                uint8_t* codes);
 hipError_t launch_sapling_bvk(hipStream_t st, int ntx, const uint32_t* off, const uint32_t* nspends,
@@ -1625,6 +1630,61 @@ extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, c
   HIPCHK(launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst));
   HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ block headers (zg_equihash.h)
+extern "C" int zg_equihash_verify(zg_ctx* ctx, int params, size_t n, const uint8_t* inputs, size_t input_len,
+                                  const uint8_t* solutions, uint8_t* ok, uint8_t* repeated) {
+  const size_t sb = (size_t)equihash_solution_bytes(params);
+  if (!ctx || !sb || input_len < 1 || input_len > 252 || (n && (!inputs || !solutions || !ok)) || n > (1u << 30))
+    return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!n) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevScratch s;
+  uint8_t *din, *dsol, *dok, *drep;
+  HIPCHK(s.alloc(&din, input_len * n));
+  HIPCHK(s.alloc(&dsol, sb * n));
+  HIPCHK(s.alloc(&dok, n));
+  HIPCHK(s.alloc(&drep, n));
+  HIPCHK(hipMemcpyAsync(din, inputs, input_len * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dsol, solutions, sb * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
+  HIPCHK(launch_equihash(ctx->stream, params, din, input_len, (int)input_len, dsol, sb, (int)n, dok, drep));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (repeated) HIPCHK(hipMemcpyAsync(repeated, drep, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return ZG_OK;
+}
+
+extern "C" int zg_headers_verify(zg_ctx* ctx, size_t n, const uint8_t* headers, uint32_t max_bits, uint8_t* status,
+                                 uint8_t* hashes, uint8_t* flags) {
+  if (!ctx || (n && (!headers || !status)) || n > (1u << 20)) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!n) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevScratch s;
+  uint8_t *dh, *dok, *drep, *dst, *dhash, *dfl;
+  HIPCHK(s.alloc(&dh, (size_t)ZG_HEADER_BYTES * n));
+  HIPCHK(s.alloc(&dok, n));
+  HIPCHK(s.alloc(&drep, n));
+  HIPCHK(s.alloc(&dst, n));
+  HIPCHK(s.alloc(&dhash, 32 * n));
+  HIPCHK(s.alloc(&dfl, n));
+  HIPCHK(hipMemcpyAsync(dh, headers, (size_t)ZG_HEADER_BYTES * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
+  HIPCHK(launch_headers(ctx->stream, dh, (int)n, max_bits, dok, drep, dst, dhash, dfl));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (hashes) HIPCHK(hipMemcpyAsync(hashes, dhash, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (flags) HIPCHK(hipMemcpyAsync(flags, dfl, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
   return ZG_OK;

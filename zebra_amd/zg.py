@@ -16,6 +16,12 @@ KIND_SPEND, KIND_OUTPUT, KIND_SPROUT = 0, 1, 2
 GEN_SPEND_AUTH, GEN_BINDING = 0, 1   # include/zg.h ZG_GEN_*
 # include/zg.h ZG_ED_*: the reference's error class of an Ed25519 JoinSplit signature check
 ED_OK, ED_PUBLIC_ENCODING, ED_SIGNATURE_ENCODING, ED_SIGNATURE = 0, 1, 2, 3
+# include/zg.h ZG_EQ_* (Equihash instances), ZG_HDR_* (the first failing header check) and ZG_HDR_F_* (every check)
+EQ_200_9, EQ_96_5, EQ_48_5 = 0, 1, 2
+EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
+HEADER_BYTES = 1487
+HDR_OK, HDR_MALFORMED, HDR_EQUIHASH, HDR_POW = 0, 1, 2, 3
+HDR_F_EQUIHASH, HDR_F_POW, HDR_F_REPEATED = 1, 2, 4
 TREE_SPROUT, TREE_SAPLING = 0, 1     # include/zg.h ZG_TREE_*
 SPROUT_HEIGHT, SAPLING_HEIGHT = 29, 32   # storage/src/tree_state.rs H29 / H32
 E_TREE_FULL = -7
@@ -80,6 +86,9 @@ def lib():
         L.zg_redjubjub_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p, u8p]
         L.zg_ed25519_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p]
         L.zg_last_sig_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.zg_equihash_verify.argtypes = [vp, ctypes.c_int, sz, u8p, sz, u8p, u8p, u8p]
+        L.zg_headers_verify.argtypes = [vp, sz, u8p, ctypes.c_uint32, u8p, u8p, u8p]
+        L.zg_pow_valid.argtypes = [ctypes.c_uint32, ctypes.c_uint32, u8p]
         L.zg_sapling_bvk.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), u8p,
                                      ctypes.POINTER(ctypes.c_int64), u8p, u8p]
         L.zg_jubjub_decode.argtypes = [vp, sz, u8p, u8p, u8p]
@@ -199,6 +208,14 @@ def debug_field_mul(field, a, b, device=0):
     if rc:
         raise ZgError(rc, "zg_debug_field_mul")
     return [out.raw[w * i:w * i + w] for i in range(n)]
+
+
+def pow_valid(max_bits, bits, hash32):
+    """is_valid_proof_of_work (verification/src/work.rs:21-34) on the CPU, the routine the header kernel
+    uses: compacts as u32, the hash in H256 storage order"""
+    if len(hash32) != 32:
+        raise ZgError(-1, "pow_valid takes a 32-byte hash")
+    return lib().zg_pow_valid(max_bits & 0xFFFFFFFF, bits & 0xFFFFFFFF, bytes(hash32)) == 1
 
 
 def pack_inputs(rows):
@@ -386,8 +403,40 @@ class Context:
                                           b"".join(map(bytes, msgs)), st))
         return list(st.raw[:n])
 
+    def equihash_verify(self, params, inputs, solutions):
+        """verify_equihash_solution per (input, solution) for the instance params (EQ_*): inputs of one
+        common length 1..252, solutions of EQ_SOLUTION_BYTES[params] -> (ok, repeated): the reference's
+        verdicts and whether some index occurs twice (lists of bool)"""
+        n = len(inputs)
+        assert len(solutions) == n
+        if params not in EQ_SOLUTION_BYTES:
+            raise ZgError(-1, "equihash_verify: unknown instance")
+        ilen = len(inputs[0]) if n else 1
+        if not (1 <= ilen <= 252 and all(len(x) == ilen for x in inputs) and
+                all(len(x) == EQ_SOLUTION_BYTES[params] for x in solutions)):
+            raise ZgError(-1, "equihash_verify takes inputs of one length 1..252 and %d-byte solutions"
+                          % EQ_SOLUTION_BYTES[params])
+        ok = ctypes.create_string_buffer(max(n, 1))
+        rep = ctypes.create_string_buffer(max(n, 1))
+        self._chk(lib().zg_equihash_verify(self._p, params, n, b"".join(map(bytes, inputs)), ilen,
+                                           b"".join(map(bytes, solutions)), ok, rep))
+        return [b == 1 for b in ok.raw[:n]], [b == 1 for b in rep.raw[:n]]
+
+    def headers_verify(self, headers, max_bits):
+        """HeaderEquihashSolution::check + HeaderProofOfWork::check over serialized 1487-byte headers, ONE
+        call -> (statuses HDR_*, block hashes in H256 storage order, flags HDR_F_* masks)"""
+        n = len(headers)
+        if not all(len(x) == HEADER_BYTES for x in headers):
+            raise ZgError(-1, "headers_verify takes %d-byte headers" % HEADER_BYTES)
+        st = ctypes.create_string_buffer(max(n, 1))
+        hs = ctypes.create_string_buffer(max(32 * n, 1))
+        fl = ctypes.create_string_buffer(max(n, 1))
+        self._chk(lib().zg_headers_verify(self._p, n, b"".join(map(bytes, headers)), max_bits & 0xFFFFFFFF, st, hs, fl))
+        return list(st.raw[:n]), [hs.raw[32 * i:32 * i + 32] for i in range(n)], list(fl.raw[:n])
+
     def last_sig_kernel_ms(self):
-        """device time of the kernel of the last ed25519_verify / redjubjub_verify call"""
+        """device time of the kernel(s) of the last ed25519_verify / redjubjub_verify / equihash_verify /
+        headers_verify call"""
         ms = ctypes.c_float(0)
         self._chk(lib().zg_last_sig_kernel_ms(self._p, ctypes.byref(ms)))
         return ms.value
