@@ -125,6 +125,10 @@ int zg_verify_each(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* 
  *   r        optional n x 16 B batch scalars (NULL: generated per zg_config)
  *   status   out, n bytes (ZG_STATUS_*), exact per proof (bisection on failure)
  *   gt_out   optional out: prod_i LHS_i^{r_i} over proofs that decoded with a well-formed VK
+ * n = 0 is an empty batch, not an error: ZG_OK, no status written (the buffers may be NULL except
+ * `status` of zg_verify_batch), gt_out = 1. In the split form zg_batch_begin(n = 0) begins a batch like any
+ * other (a second begin is ZG_E_STATE), zg_batch_partial gives the empty product 1, which passes
+ * zg_gt_check, and zg_batch_finish ends it with either verdict without writing a status.
  */
 int zg_verify_batch(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* kinds, const uint8_t* inputs,
                     const uint8_t* n_inputs, const uint8_t* r, uint8_t* status, uint8_t* gt_out);

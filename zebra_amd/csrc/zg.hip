@@ -929,7 +929,11 @@ static int run_pipeline(zg_ctx* ctx) {
   // the group chains run on the side stream in parts (below): with pairs_late the root's VK MSM + pairs
   // follow the last chain part there instead of preceding the first (8k with line products, r05aa: the
   // first chain waited 2.8 ms behind k_node_pairs although its part was formed)
-  const bool late = lineprod && ctx->lp_parts != 1 && ctx->pairs_late && !ctx->serial_side;
+  // (only when the chains do run in parts: a batch of few groups forms its line products in one part on
+  // the main stream, and nothing would launch the deferred pairs)
+  int bounds[ZG_LP_PARTS_MAX + 1];
+  const int parts = lineprod ? lineprod_parts(ctx->lp_parts, (int)(ctx->npad / gsize), ctx->ncu, bounds) : 1;
+  const bool late = lineprod && parts > 1 && ctx->pairs_late && !ctx->serial_side;
   if (!ctx->serial_side) {
     HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev[1], 0));
     if ((rc = side_k4(ctx->side))) return rc;
@@ -968,8 +972,6 @@ static int run_pipeline(zg_ctx* ctx) {
       // chains over part k while the main stream forms part k + 1, so the chains' latency hides
       // behind the line products except for the last part
       const int m = (int)(ctx->npad / gsize);
-      int bounds[ZG_LP_PARTS_MAX + 1];
-      const int parts = lineprod_parts(ctx->lp_parts, m, ctx->ncu, bounds);
       if (parts <= 1) {
         HIPCHK(launch_prog_lineprod(ctx->stream, b, (const Fq2*)ctx->d_lines, ctx->d_lprod, gsize, 0, ZG_NCOEFF,
                                           ctx->quad_split, affine));
