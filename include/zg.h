@@ -257,8 +257,8 @@ int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* stat
  *          ZG_ED_SIGNATURE           compress([S]B + [k](-A)) != the 32 bytes of R, k = SHA-512(R ||
  *                                    pubkey || msg) mod l; cofactorless; a non-canonical R never verifies
  *   zg_last_sig_kernel_ms: device time (HIP events on the context stream) of the kernel(s) of the most
- *        recent zg_ed25519_verify, zg_redjubjub_verify, zg_equihash_verify or zg_headers_verify on this
- *        context (measurement helper) */
+ *        recent zg_ed25519_verify, zg_ecdsa_verify, zg_redjubjub_verify, zg_equihash_verify or
+ *        zg_headers_verify on this context (measurement helper) */
 #define ZG_ED_OK 0
 #define ZG_ED_PUBLIC_ENCODING 1    /* Error::InvalidPublicEncoding */
 #define ZG_ED_SIGNATURE_ENCODING 2 /* Error::InvalidSignatureEncoding */
@@ -266,6 +266,35 @@ int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* stat
 int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
                       uint8_t* status);
 int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms);
+
+/* ---- transparent input signatures on the GPU: secp256k1 ECDSA, batched. Any n;
+ * device memory per call, n = 0 and the argument checks as zg_ed25519_verify; sig_off must not decrease.
+ *   zg_ecdsa_verify <- TransactionSignatureChecker::verify_signature script/src/verify.rs:60-67
+ *        -> keys::Public::verify keys/src/public.rs:38-49 -> eth-secp256k1 (libsecp256k1,
+ *        keys/Cargo.toml:11). The script interpreter and the sighash stay with the caller.
+ *        pubkeys n x ZG_ECDSA_PUBKEY_STRIDE; pubkey_len[i] the key's length (a value other than 33 or 65
+ *        is ZG_ECDSA_PUBLIC and the bytes are not read); sigs the DER signatures back to back, each
+ *        without its hashtype byte, any length including 0; sig_off n + 1 offsets into sigs (no byte
+ *        outside [sig_off[i], sig_off[i+1]) is read for item i, whatever its length bytes claim); msg
+ *        n x 32, the sighash as Message holds it (big-endian) -> status n; the checks run in this order
+ *        and the first failing one is the status:
+ *          ZG_ECDSA_PUBLIC              Public::from_slice / PublicKey::from_slice fails: 33 bytes with
+ *                                       prefix 02/03 (x < p, a root of x^3 + 7 exists) or 65 bytes with
+ *                                       prefix 04/06/07 (x, y < p, on the curve, 06/07: parity of y)
+ *          ZG_ECDSA_SIGNATURE_ENCODING  Signature::from_der_lax fails (lax_der_parsing.c: sequence length
+ *                                       ignored, long-form integer lengths, no sign check, trailing bytes
+ *                                       ignored; an integer >= n or longer than 32 bytes is not a failure:
+ *                                       r = s = 0)
+ *          ZG_ECDSA_SIGNATURE           verify is false: r or s zero, (m/s) G + (r/s) Q at infinity, or its
+ *                                       x is neither r nor (when r + n < p) r + n; m = msg mod n.
+ *        Every non-zero status is `false` at the script level (verify.rs: unwrap_or(false)). */
+#define ZG_ECDSA_OK 0
+#define ZG_ECDSA_PUBLIC 1              /* keys::Error::InvalidPublic */
+#define ZG_ECDSA_SIGNATURE_ENCODING 2  /* keys::Error::InvalidSignature (from_der_lax) */
+#define ZG_ECDSA_SIGNATURE 3           /* Ok(false) */
+#define ZG_ECDSA_PUBKEY_STRIDE 65
+int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* pubkey_len, const uint8_t* sigs,
+                    const uint32_t* sig_off, const uint8_t* msg, uint8_t* status);
 
 /* ---- block headers on the GPU: the Equihash solution, the block hash and the
  * proof of work of HeaderVerifier::check (verification/src/verify_header.rs:26-32), batched. Any n
@@ -423,7 +452,9 @@ int zg_bench_mad_rate_clock(zg_ctx* ctx, double* macs_per_s, double* clock_hz);
  * 2: Fq2 (96 B = c0 || c1; a lazy < 2p per coefficient, b canonical), 3: BLS12-381 Fr a b 2^-256 mod r
  * (32 B), 4: BN254 Fq a b 2^-256 mod q (32 B), 5: a b mod 2^255 - 19 (the 9 x 29-bit-digit product of
  * zg_ed25519.h; 32-B LE operands of any value < 2^256, canonical result), 6: (a + b 2^256) mod l, l the
- * Ed25519 group order (32-B operands of any value, canonical result). out has the operands' size. */
+ * Ed25519 group order (32-B operands of any value, canonical result), 7: a b mod 2^256 - 2^32 - 977 (the
+ * 9 x 29-bit-digit product of zg_ecdsa.h; 32-B LE operands of any value < 2^256, canonical result), 8: a b
+ * mod n, n the secp256k1 group order (same operands and result). out has the operands' size. */
 int zg_debug_field_mul(int device, int field, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 
 #ifdef __cplusplus

@@ -22,11 +22,13 @@
 //! Backends: `GpuVerifier` (the product) and `cpu::CpuBackend` (the reference's own per-proof
 //! calls). `verify_block_or_cpu` runs the window on the GPU and, on a GpuError, re-runs the
 //! whole window on the CPU backend, so an import never stops on a device fault.
+use std::collections::HashMap;
 use std::convert::TryInto;
+use std::sync::Arc;
 
 use super::cpu::CpuBackend;
 use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, Item};
-use super::ffi::{ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
+use super::ffi::{ZG_ECDSA_OK, ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
                  ZG_PREP_KIND_OUTPUT, ZG_PREP_KIND_SPEND};
 use super::{ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_KIND_SPROUT, ZG_STATUS_OK};
 
@@ -70,6 +72,23 @@ pub struct Output {
     pub zkproof: [u8; 192],
 }
 
+/// one signature check a script run asked its checker for (TransactionSignatureChecker::
+/// verify_signature, script/src/verify.rs:60-67): the key and the DER signature without its hashtype
+/// byte as the script pushed them, and the 32-byte sighash of that input
+#[derive(Clone)]
+pub struct EcdsaCheck {
+    pub input_index: usize,
+    pub pubkey: Vec<u8>,
+    pub sig: Vec<u8>,
+    pub sighash: [u8; 32],
+}
+
+/// lookup(pubkey, sig, sighash) -> the signature check's verdict
+pub type EcdsaLookup<'a> = dyn FnMut(&[u8], &[u8], &[u8; 32]) -> Result<bool, GpuError> + 'a;
+/// the caller's second TransactionEval::check (accept_transaction.rs:363-422) with `lookup` as the
+/// checker: the reference's eval error, or None
+pub type EvalRerun = Arc<dyn Fn(&mut EcdsaLookup) -> Result<Option<TxError>, GpuError> + Send + Sync>;
+
 #[derive(Default, Clone)]
 pub struct Tx {
     /// first failing check before the JoinSplit stage (version ... eval)
@@ -92,11 +111,20 @@ pub struct Tx {
     /// the Ed25519 JoinSplit signature over the same sighash (accept_transaction.rs:649-653): with
     /// it (and js_pubkey, sighash) the signature is verified on the GPU instead of js_sig_ok
     pub js_sig: Option<[u8; 64]>,
+    /// the transparent inputs' ECDSA checks, recorded by one run of
+    /// TransactionEval::check with a checker that answers true: all of the window's are verified in ONE
+    /// zg_ecdsa_verify call; if every one of a transaction's is ZG_ECDSA_OK that run was the
+    /// reference's run (pre_error then covers only the checks before eval) ...
+    pub ecdsa_checks: Vec<EcdsaCheck>,
+    /// ... otherwise this repeats the run with the real verdicts and its value is the eval error
+    pub eval_rerun: Option<EvalRerun>,
 }
 
 #[derive(Debug, Clone, PartialEq)]
 pub enum TxError {
     Caller(String),
+    /// TransactionError::Signature(input index, script error) of the eval stage, from eval_rerun
+    Signature(usize, String),
     JoinSplitSignature,
     InvalidJoinSplit(usize),
     InvalidSapling,
@@ -114,6 +142,8 @@ pub trait Backend {
     fn sapling_bvk(&self, txs: &[(Vec<[u8; 32]>, Vec<[u8; 32]>, i64)]) -> Result<Vec<(u8, [u8; 32])>, GpuError>;
     /// Ed25519 statuses (ZG_ED_*) for (pubkey, signature, 32-byte message)
     fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError>;
+    /// ECDSA statuses (ZG_ECDSA_*) for (public key, DER signature, 32-byte sighash)
+    fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError>;
     /// header statuses (ZG_HDR_*: the first failing of deserialize / Equihash / proof of work) for
     /// serialized 1487-byte headers against the compact `max_bits`
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError>;
@@ -140,6 +170,9 @@ impl Backend for GpuVerifier {
     }
     fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
         GpuVerifier::ed25519_verify(self, items)
+    }
+    fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        GpuVerifier::ecdsa_verify(self, items)
     }
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
         Ok(GpuVerifier::headers_verify(self, headers, max_bits)?.into_iter().map(|r| r.0).collect())
@@ -367,11 +400,51 @@ fn js_sig_verdicts<B: Backend>(v: &B, txs: &[Tx]) -> Result<Vec<bool>, GpuError>
     Ok(ok)
 }
 
+type EcdsaKey = (Vec<u8>, Vec<u8>, [u8; 32]);
+
+/// the verdict table of the window's recorded ECDSA checks: ONE ecdsa_verify call for all of them (any
+/// non-zero status is false, verify.rs:60-67 unwrap_or(false))
+fn ecdsa_table<B: Backend>(v: &B, txs: &[Tx]) -> Result<HashMap<EcdsaKey, bool>, GpuError> {
+    let keys: Vec<EcdsaKey> =
+        txs.iter().flat_map(|t| t.ecdsa_checks.iter().map(|c| (c.pubkey.clone(), c.sig.clone(), c.sighash))).collect();
+    if keys.is_empty() {
+        return Ok(HashMap::new());
+    }
+    let sts = v.ecdsa_verify(&keys)?;
+    Ok(keys.into_iter().zip(sts).map(|(k, st)| (k, st == ZG_ECDSA_OK)).collect())
+}
+
+/// the eval error of one transaction: None when every recorded check is ZG_ECDSA_OK, else eval_rerun's
+/// value with the table as the checker; a triple the optimistic runs never asked for (OP_CHECKMULTISIG
+/// tries other pairs once one fails) is verified in a further call
+fn eval_error<B: Backend>(v: &B, tx: &Tx, table: &mut HashMap<EcdsaKey, bool>) -> Result<Option<TxError>, GpuError> {
+    if tx.ecdsa_checks.iter().all(|c| table[&(c.pubkey.clone(), c.sig.clone(), c.sighash)]) {
+        return Ok(None);
+    }
+    let rerun = match &tx.eval_rerun {
+        Some(r) => r.clone(),
+        None => return Err(GpuError { code: -1, message: "a transaction's ECDSA check failed but it carries no eval_rerun".to_string() }),
+    };
+    let mut lookup = |pk: &[u8], sig: &[u8], sighash: &[u8; 32]| -> Result<bool, GpuError> {
+        let k = (pk.to_vec(), sig.to_vec(), *sighash);
+        if let Some(ok) = table.get(&k) {
+            return Ok(*ok);
+        }
+        let ok = v.ecdsa_verify(&[k.clone()])?[0] == ZG_ECDSA_OK;
+        table.insert(k, ok);
+        Ok(ok)
+    };
+    (*rerun)(&mut lookup)
+}
+
 fn tx_error(tx: &Tx, plan: &(Vec<Plan>, Vec<Plan>, Vec<Plan>), status: &[u8], pghr_status: &[u8], sp_ok: &[bool],
-            bind_ok: bool, js_sig_ok: bool) -> Option<TxError> {
+            bind_ok: bool, js_sig_ok: bool, eval: Option<TxError>) -> Option<TxError> {
     let (js, sp, out) = plan;
     if let Some(e) = &tx.pre_error {
         return Some(TxError::Caller(e.clone()));
+    }
+    if eval.is_some() {
+        return eval;
     }
     if !tx.joinsplits.is_empty() {
         if !js_sig_ok {
@@ -433,8 +506,11 @@ pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxEr
     let pghr_status = if pghr.is_empty() { Vec::new() } else { v.pghr13_verify(&pghr)? };
     let (sp_ok, bind_ok) = sig_verdicts(v, txs)?;
     let js_ok = js_sig_verdicts(v, txs)?;
+    let mut table = ecdsa_table(v, txs)?;
     for (idx, (tx, plan)) in txs.iter().zip(&plans).enumerate() {
-        if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx], js_ok[idx]) {
+        // precedence: pre_error, then the eval error, then the JoinSplit and Sapling stages
+        let eval = if tx.pre_error.is_none() && !tx.ecdsa_checks.is_empty() { eval_error(v, tx, &mut table)? } else { None };
+        if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx], js_ok[idx], eval) {
             return Ok(Some((idx, e)));
         }
     }

@@ -28,6 +28,7 @@ use crypto::sapling_crypto::redjubjub::{self, Signature};
 use crypto::{pghr13_verify, Groth16VerifyingKey, Pghr13Proof, Pghr13VerifyingKey, JUBJUB};
 
 use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_MALFORMED, ZG_HDR_OK, ZG_HDR_POW};
+use super::ffi::{ZG_ECDSA_OK, ZG_ECDSA_PUBLIC, ZG_ECDSA_SIGNATURE, ZG_ECDSA_SIGNATURE_ENCODING};
 use super::ffi::{ZG_ED_OK, ZG_ED_PUBLIC_ENCODING, ZG_ED_SIGNATURE, ZG_ED_SIGNATURE_ENCODING, ZG_GEN_BINDING,
                  ZG_STATUS_INPUT_NONCANONICAL};
 use super::{GpuError, Item, ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_STATUS_DECODE_INVALID, ZG_STATUS_MALFORMED_VK,
@@ -141,6 +142,27 @@ impl<'a> super::collect::Backend for CpuBackend<'a> {
                     FixedGenerators::SpendingKeyGenerator
                 };
                 key.verify(&msg[..], &sig, g, &JUBJUB)
+            })
+            .collect())
+    }
+
+    /// keys::Public::from_slice + verify for every (public key, DER signature, sighash), the outcome as
+    /// ZG_ECDSA_* (script/src/verify.rs:60-67, keys/src/public.rs:18-49)
+    fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        Ok(items
+            .par_iter()
+            .map(|(pk, sig, msg)| {
+                let public = match ::keys::Public::from_slice(pk) {
+                    Ok(p) => p,
+                    Err(_) => return ZG_ECDSA_PUBLIC,
+                };
+                let message: ::keys::Message = msg[..].into();
+                match public.verify(&message, &::keys::Signature::from(sig.clone())) {
+                    Ok(true) => ZG_ECDSA_OK,
+                    Ok(false) => ZG_ECDSA_SIGNATURE,
+                    Err(::keys::Error::InvalidPublic) => ZG_ECDSA_PUBLIC,
+                    Err(_) => ZG_ECDSA_SIGNATURE_ENCODING,
+                }
             })
             .collect())
     }

@@ -62,6 +62,13 @@ pub const ZG_ED_OK: u8 = 0;
 pub const ZG_ED_PUBLIC_ENCODING: u8 = 1;
 pub const ZG_ED_SIGNATURE_ENCODING: u8 = 2;
 pub const ZG_ED_SIGNATURE: u8 = 3;
+// zg_ecdsa_verify statuses: keys::Public::verify of a transparent input's signature (Ok(true), Error::InvalidPublic,
+// Error::InvalidSignature from from_der_lax, Ok(false)) and the stride of one key in `pubkeys`
+pub const ZG_ECDSA_OK: u8 = 0;
+pub const ZG_ECDSA_PUBLIC: u8 = 1;
+pub const ZG_ECDSA_SIGNATURE_ENCODING: u8 = 2;
+pub const ZG_ECDSA_SIGNATURE: u8 = 3;
+pub const ZG_ECDSA_PUBKEY_STRIDE: usize = 65;
 // zg_equihash_verify instances, zg_headers_verify statuses (the first failing check) and flags (every check)
 pub const ZG_EQ_200_9: c_int = 0;
 pub const ZG_EQ_96_5: c_int = 1;
@@ -140,6 +147,8 @@ extern "C" {
     pub fn zg_jubjub_decode(ctx: *mut ZgCtx, n: usize, points: *const u8, status: *mut u8, xy: *mut u8) -> c_int;
     pub fn zg_ed25519_verify(ctx: *mut ZgCtx, n: usize, pubkey: *const u8, sig: *const u8, msg: *const u8,
                              status: *mut u8) -> c_int;
+    pub fn zg_ecdsa_verify(ctx: *mut ZgCtx, n: usize, pubkeys: *const u8, pubkey_len: *const u8, sigs: *const u8,
+                           sig_off: *const u32, msg: *const u8, status: *mut u8) -> c_int;
     pub fn zg_last_sig_kernel_ms(ctx: *mut ZgCtx, ms: *mut f32) -> c_int;
     pub fn zg_equihash_verify(ctx: *mut ZgCtx, params: c_int, n: usize, inputs: *const u8, input_len: usize,
                               solutions: *const u8, ok: *mut u8, repeated: *mut u8) -> c_int;

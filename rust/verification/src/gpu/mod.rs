@@ -190,6 +190,39 @@ impl GpuVerifier {
         Ok(status)
     }
 
+    /// secp256k1 ECDSA checks of transparent inputs (TransactionSignatureChecker::verify_signature,
+    /// script/src/verify.rs:60-67 -> keys::Public::verify, keys/src/public.rs:38-49): per item (public
+    /// key as pushed, DER signature without its hashtype byte, the 32-byte sighash) -> ZG_ECDSA_* (OK,
+    /// PUBLIC, SIGNATURE_ENCODING, SIGNATURE). A key longer than 255 bytes is sent as length 0.
+    pub fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let n = items.len();
+        let mut pk = vec![0u8; ffi::ZG_ECDSA_PUBKEY_STRIDE * n];
+        let mut len = Vec::with_capacity(n);
+        let mut sig = Vec::new();
+        let mut off = Vec::with_capacity(n + 1);
+        let mut msg = Vec::with_capacity(32 * n);
+        for (i, (p, s, m)) in items.iter().enumerate() {
+            let k = p.len().min(ffi::ZG_ECDSA_PUBKEY_STRIDE);
+            pk[ffi::ZG_ECDSA_PUBKEY_STRIDE * i..ffi::ZG_ECDSA_PUBKEY_STRIDE * i + k].copy_from_slice(&p[..k]);
+            len.push(if p.len() <= 255 { p.len() as u8 } else { 0 });
+            off.push(sig.len() as u32);
+            sig.extend_from_slice(s);
+            msg.extend_from_slice(m);
+        }
+        if sig.len() > u32::max_value() as usize {
+            return Err(GpuError { code: -1, message: "ecdsa_verify: the signatures exceed 4 GiB".to_string() });
+        }
+        off.push(sig.len() as u32);
+        sig.push(0);
+        let mut status = vec![0u8; n];
+        check(self.ctx, unsafe {
+            ffi::zg_ecdsa_verify(self.ctx, n, pk.as_ptr(), len.as_ptr(), sig.as_ptr(), off.as_ptr(), msg.as_ptr(),
+                                 status.as_mut_ptr())
+        })?;
+        Ok(status)
+    }
+
     /// verify_equihash_solution (equihash.rs:80-172) for the instance `params` (ffi::ZG_EQ_*): per item
     /// (input, solution), inputs of one common length 1..=252 -> (ok, repeated) per item. `ok` is the
     /// reference's verdict, which accepts some solutions with a repeated index (distinct_indices,

@@ -359,6 +359,9 @@ mod tests {
         fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError> {
             Ok(vec![0; items.len()])
         }
+        fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError> {
+            Ok(vec![0; items.len()])
+        }
         fn headers_verify(&self, headers: &[Vec<u8>], _max_bits: u32) -> Result<Vec<u8>, GpuError> {
             Ok(vec![0; headers.len()])
         }

@@ -21,7 +21,12 @@ The checks that are not proofs or signatures (tree roots, nullifiers, the transp
 before the shielded stages) are evaluated by the caller exactly as today and handed in as
 outcomes; the Ed25519 JoinSplit signature too, unless the transaction carries it (Tx.js_sig):
 then every such signature of the window is verified in ONE zg_ed25519_verify call (SURVEY.md 8(f)
-f5; accept_transaction.rs:649-653 -> crypto::verify_ed25519 crypto/src/lib.rs:298-305); the collector prepares every public input of
+f5; accept_transaction.rs:649-653 -> crypto::verify_ed25519 crypto/src/lib.rs:298-305). The script
+interpreter of the transparent inputs stays with the caller too, but the secp256k1 signature checks
+under it can be handed in (Tx.ecdsa_checks, SURVEY.md 8(f) f7): the caller runs TransactionEval::check
+(accept_transaction.rs:363-422) once with a recording checker that answers true, every recorded check
+of the window is verified in ONE zg_ecdsa_verify call, and only a transaction with a failed check has
+its script run repeated with the real verdicts (Tx.eval_rerun). The collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
 verifies all Groth16 proofs of the window in
@@ -32,7 +37,7 @@ re-injects the per-proof statuses in reference order: a PHGR description that fa
 the transaction's descriptions, before its tree_cache.continue_root (accept_transaction.rs:575-592).
 """
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 from . import zg
 
@@ -76,6 +81,17 @@ class Output:
 
 
 @dataclass
+class EcdsaCheck:
+    """one signature check a script run asked its checker for (TransactionSignatureChecker::
+    verify_signature, script/src/verify.rs:60-67): the key and the DER signature without its hashtype
+    byte as the script pushed them, and the 32-byte sighash of that input"""
+    input_index: int
+    pubkey: bytes
+    sig: bytes
+    sighash: bytes
+
+
+@dataclass
 class Tx:
     """the shielded-proof view of one transaction, with the caller's non-Groth16 outcomes"""
     pre_error: Optional[str] = None           # first failing check before the JoinSplit stage
@@ -95,6 +111,14 @@ class Tx:
     # the JoinSplit signature on the GPU: the 64-byte Ed25519 signature over the
     # same sighash, checked against js_pubkey (accept_transaction.rs:649-653)
     js_sig: Optional[bytes] = None
+    # the transparent inputs' ECDSA checks on the GPU. A script's run depends on its
+    # checker only through the booleans it returns, so the caller runs TransactionEval::check once with a
+    # recording checker that answers true and notes every check here; if the GPU confirms them all, that
+    # run was the reference's run (and pre_error, which then covers only the checks before eval, stands).
+    # Otherwise eval_rerun(lookup) repeats the run with lookup(pubkey, sig, sighash) -> bool as the
+    # checker and returns the reference's eval error, or None
+    ecdsa_checks: List[EcdsaCheck] = field(default_factory=list)
+    eval_rerun: Optional[Callable] = None
 
 
 _POOL = None
@@ -300,8 +324,43 @@ def _js_sig_verdicts(txs, ctx, verify_js_sigs):
     return ok
 
 
-def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None):
-    """the reference's first error of one transaction, given the proof statuses"""
+def _eval_errors(txs, ctx, verify_ecdsa):
+    """-> eval_error(tx): the reference's TransactionEval error of a transaction (None: the scripts pass).
+    Every recorded check of the window goes through ONE verify_ecdsa call; a transaction whose checks are
+    all ECDSA_OK has no eval error (its optimistic run was the reference's run); for any other one the
+    error is tx.eval_rerun(lookup), used verbatim. lookup answers from the window's table; a triple the
+    optimistic runs never asked for (OP_CHECKMULTISIG tries other pairs once one fails) is verified in a
+    further call. Any non-zero status is false (verify.rs:60-67: unwrap_or(false))."""
+    checks = [c for tx in txs for c in tx.ecdsa_checks]
+    if not checks:
+        return lambda tx: None
+    if verify_ecdsa is None:
+        if ctx is None:
+            raise zg.ZgError(-1, "transactions carry ECDSA checks but no ECDSA backend was given "
+                                 "(pass ctx= or verify_ecdsa=)")
+        verify_ecdsa = ctx.ecdsa_verify
+    keys = [(bytes(c.pubkey), bytes(c.sig), bytes(c.sighash)) for c in checks]
+    sts = verify_ecdsa([k[0] for k in keys], [k[1] for k in keys], [k[2] for k in keys])
+    table = {k: st == zg.ECDSA_OK for k, st in zip(keys, sts)}
+
+    def lookup(pubkey, sig, sighash):
+        k = (bytes(pubkey), bytes(sig), bytes(sighash))
+        if k not in table:
+            table[k] = verify_ecdsa([k[0]], [k[1]], [k[2]])[0] == zg.ECDSA_OK
+        return table[k]
+
+    def eval_error(tx):
+        if all(table[(bytes(c.pubkey), bytes(c.sig), bytes(c.sighash))] for c in tx.ecdsa_checks):
+            return None
+        if tx.eval_rerun is None:
+            raise zg.ZgError(-1, "a transaction's ECDSA check failed but it carries no eval_rerun")
+        return tx.eval_rerun(lookup)
+    return eval_error
+
+
+def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None, eval_error=None):
+    """the reference's first error of one transaction, given the proof statuses; eval_error(tx) is asked
+    only when no earlier check failed"""
     if js_sig_ok is None:
         js_sig_ok = tx.js_sig_ok
     js_plan, sp_plan, out_plan = plan
@@ -311,6 +370,10 @@ def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig
         bind_ok = tx.binding_ok
     if tx.pre_error:
         return tx.pre_error
+    if eval_error is not None and tx.ecdsa_checks:
+        err = eval_error(tx)
+        if err is not None:
+            return err
     if tx.joinsplits:
         if not js_sig_ok:
             return "JoinSplitSignature"
@@ -355,7 +418,7 @@ def _chunked(verify, cap):
 
 
 def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
-                 verify_js_sigs=None):
+                 verify_js_sigs=None, verify_ecdsa=None):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -369,7 +432,11 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     ctx.pghr13_verify (ONE zg_pghr13_verify call for the window). Transactions that carry their
     JoinSplit signature (Tx.js_sig, with js_pubkey and sighash) get it verified through
     verify_js_sigs(pubkeys, sigs, msgs) -> ED_* statuses, default ctx.ed25519_verify (ONE
-    zg_ed25519_verify call for the window); the others keep the caller's js_sig_ok."""
+    zg_ed25519_verify call for the window); the others keep the caller's js_sig_ok. The recorded
+    ECDSA checks of the transparent inputs (Tx.ecdsa_checks) go through verify_ecdsa(pubkeys, sigs,
+    msgs) -> ECDSA_* statuses, default ctx.ecdsa_verify (ONE zg_ecdsa_verify call for the window); the
+    eval error of a transaction with a failed check is its eval_rerun's, placed after pre_error and
+    before the JoinSplit and Sapling stages (accept_transaction.rs:68-84)."""
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:
         def verify(proofs, kinds, inputs, n_inputs):
@@ -394,8 +461,9 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
         pghr_status = list(verify_pghr([p for p, _ in pghr], [inp for _, inp in pghr]))
     sp_ok, bind_ok = _sig_verdicts(txs, ctx, verify_sigs, sapling_bvk)
     js_ok = _js_sig_verdicts(txs, ctx, verify_js_sigs)
+    eval_error = _eval_errors(txs, ctx, verify_ecdsa)
     for idx, (tx, plan) in enumerate(zip(txs, plans)):
-        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx])
+        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx], eval_error)
         if err is not None:
             return idx, err
     return None

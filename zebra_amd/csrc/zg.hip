@@ -104,6 +104,7 @@ struct zg_dev {
   std::vector<VKEntry*> vks;  // prepare_verifying_key once per distinct key per device
   uint32_t* jj_comb = nullptr;  // Jubjub generators' comb tables (zg_jubjub.h), built on first use
   uint32_t* ed_comb = nullptr;  // the Ed25519 base point's comb table (zg_ed25519.h), built on first use
+  uint32_t* ec_comb = nullptr;  // the secp256k1 generator's comb table (zg_ecdsa.h), built on first use
   zg::MerkleDev* merkle = nullptr;  // Pedersen table + empty roots (zg_merkle.hip), first use
   zg::BnDev* bn = nullptr;          // PGHR13 key, line and comb tables (zg_pghr13.hip), first use
   std::atomic<int> inflight{0};     // contexts on this device with a batch begun and not finished
@@ -269,6 +270,7 @@ static void dev_release(zg_dev* d) {
   }
   if (d->jj_comb) hipFree(d->jj_comb);
   if (d->ed_comb) hipFree(d->ed_comb);
+  if (d->ec_comb) hipFree(d->ec_comb);
   merkle_dev_free(d->merkle);
   bn_dev_free(d->bn);
   g_devs[d->device] = nullptr;
@@ -789,6 +791,9 @@ hipError_t launch_redjubjub(hipStream_t st, const uint8_t* vk, const uint8_t* si
                             const uint8_t* gen, int n, const uint32_t* comb, uint8_t* ok);
 hipError_t launch_jj_decode(hipStream_t st, const uint8_t* pts, int n, uint8_t* status, uint8_t* xy);
 hipError_t launch_ed_comb(hipStream_t st, uint32_t* table);                                    // zg_ed25519.hip
+hipError_t launch_ec_comb(hipStream_t st, uint32_t* table);                                    // zg_ecdsa.hip
+hipError_t launch_ecdsa(hipStream_t st, const uint8_t* pubkeys, const uint8_t* pubkey_len, const uint8_t* sigs,
+                        const uint32_t* sig_off, const uint8_t* msg, int n, const uint32_t* comb, uint8_t* status);
 hipError_t launch_ed25519(hipStream_t st, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg, int n,
                           const uint32_t* comb, uint8_t* status);
 int equihash_solution_bytes(int params);                                                      // zg_equihash.hip
@@ -1630,6 +1635,64 @@ extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, c
   HIPCHK(sig_events(ctx));
   HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
   HIPCHK(launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ transparent input signatures (zg_ecdsa.h)
+#define ZG_EC_COMB_BYTES (sizeof(uint32_t) * 18 * (size_t)(32 * 255))
+static int ec_comb(zg_ctx* ctx, const uint32_t** out) {
+  zg_dev* d = ctx->dev;
+  std::lock_guard<std::mutex> g(d->mu);
+  if (!d->ec_comb) {
+    uint32_t* t = nullptr;
+    HIPCHK(hipMalloc(&t, ZG_EC_COMB_BYTES));
+    hipError_t e = launch_ec_comb(ctx->stream, t);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      hipFree(t);
+      return fail(ctx, ZG_E_HIP, std::string("secp256k1 comb table: ") + hipGetErrorString(e));
+    }
+    d->ec_comb = t;
+  }
+  *out = d->ec_comb;
+  return ZG_OK;
+}
+
+extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* pubkey_len,
+                               const uint8_t* sigs, const uint32_t* sig_off, const uint8_t* msg, uint8_t* status) {
+  if (!ctx || (n && (!pubkeys || !pubkey_len || !sigs || !sig_off || !msg || !status)) || n > (1u << 30))
+    return ZG_E_INVAL;
+  for (size_t i = 0; i < n; i++)  // a lane reads sigs[sig_off[i] .. sig_off[i+1]) of a buffer of sig_off[n] bytes
+    if (sig_off[i + 1] < sig_off[i]) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!n) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint32_t* comb = nullptr;
+  int rc = ec_comb(ctx, &comb);
+  if (rc) return rc;
+  const size_t sig_bytes = (size_t)sig_off[n] - sig_off[0];
+  DevScratch s;
+  uint8_t *dpk, *dlen, *dsig, *dmsg, *dst;
+  uint32_t* doff;
+  HIPCHK(s.alloc(&dpk, ZG_ECDSA_PUBKEY_STRIDE * n));
+  HIPCHK(s.alloc(&dlen, n));
+  HIPCHK(s.alloc(&dsig, sig_bytes ? sig_bytes : 1));
+  HIPCHK(s.alloc(&doff, sizeof(uint32_t) * (n + 1)));
+  HIPCHK(s.alloc(&dmsg, 32 * n));
+  HIPCHK(s.alloc(&dst, n));
+  HIPCHK(hipMemcpyAsync(dpk, pubkeys, ZG_ECDSA_PUBKEY_STRIDE * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dlen, pubkey_len, n, hipMemcpyHostToDevice, ctx->stream));
+  if (sig_bytes) HIPCHK(hipMemcpyAsync(dsig, sigs + sig_off[0], sig_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(doff, sig_off, sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
+  // the device buffer starts at sig_off[0]: the kernel subtracts it
+  HIPCHK(launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, dmsg, (int)n, comb, dst));
   HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));

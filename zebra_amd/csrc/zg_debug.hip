@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/zg.h"
+#include "zg_ecdsa.h"
 #include "zg_ed25519.h"
 #include "zg_field.h"
 
@@ -18,7 +19,8 @@ namespace zg {
 
 // field: 0 Fq product (fq29_mul), 1 Fq square (fq29_sqr, b unused), 2 Fq2 product (f2_mul29,
 // a lazy < 2p per coefficient), 3 Fr product (fr29_mul), 4 BN254 Fq product (bq29_mul), 5 the product
-// mod 2^255 - 19 (fe_mul, canonical out), 6 (a + b 2^256) mod l (ed_mod_l).
+// mod 2^255 - 19 (fe_mul, canonical out), 6 (a + b 2^256) mod l (ed_mod_l), 7 the product mod the
+// secp256k1 field prime (sf_mul, canonical out), 8 the product mod the secp256k1 group order (sc_mul).
 __global__ void k_debug_field(int field, int n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -35,6 +37,8 @@ __global__ void k_debug_field(int field, int n, const uint32_t* a, const uint32_
     case 3: fr29_mul(r, x, y); break;
     case 5: ed_debug_fe_mul(r, x, y); break;
     case 6: ed_debug_mod_l(r, x, y); break;
+    case 7: ec_debug_sf_mul(r, x, y); break;
+    case 8: ec_debug_sc_mul(r, x, y); break;
     default: bq29_mul(r, x, y); break;
   }
   for (int k = 0; k < w; k++) out[(size_t)i * w + k] = r[k];
@@ -44,7 +48,7 @@ __global__ void k_debug_field(int field, int n, const uint32_t* a, const uint32_
 
 extern "C" int zg_debug_field_mul(int device, int field, size_t n, const uint8_t* a, const uint8_t* b,
                                   uint8_t* out) {
-  if (field < 0 || field > 6 || (n && (!a || !b || !out)) || n > (1u << 24)) return ZG_E_INVAL;
+  if (field < 0 || field > 8 || (n && (!a || !b || !out)) || n > (1u << 24)) return ZG_E_INVAL;
   if (!n) return ZG_OK;
   const size_t bytes = n * (field == 2 ? 96 : field <= 1 ? 48 : 32);
   if (hipSetDevice(device) != hipSuccess) return ZG_E_HIP;

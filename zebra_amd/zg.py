@@ -16,6 +16,10 @@ KIND_SPEND, KIND_OUTPUT, KIND_SPROUT = 0, 1, 2
 GEN_SPEND_AUTH, GEN_BINDING = 0, 1   # include/zg.h ZG_GEN_*
 # include/zg.h ZG_ED_*: the reference's error class of an Ed25519 JoinSplit signature check
 ED_OK, ED_PUBLIC_ENCODING, ED_SIGNATURE_ENCODING, ED_SIGNATURE = 0, 1, 2, 3
+# include/zg.h ZG_ECDSA_*: keys::Public::verify of a transparent input's signature (Ok(true), Error::InvalidPublic,
+# Error::InvalidSignature, Ok(false)); the stride of one key in zg_ecdsa_verify's pubkeys
+ECDSA_OK, ECDSA_PUBLIC, ECDSA_SIGNATURE_ENCODING, ECDSA_SIGNATURE = 0, 1, 2, 3
+ECDSA_PUBKEY_STRIDE = 65
 # include/zg.h ZG_EQ_* (Equihash instances), ZG_HDR_* (the first failing header check) and ZG_HDR_F_* (every check)
 EQ_200_9, EQ_96_5, EQ_48_5 = 0, 1, 2
 EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
@@ -85,6 +89,7 @@ def lib():
         L.zg_chacha20_blocks.argtypes = [vp, u8p, u8p, ctypes.c_uint32, ctypes.c_size_t, u8p]
         L.zg_redjubjub_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p, u8p]
         L.zg_ed25519_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p]
+        L.zg_ecdsa_verify.argtypes = [vp, sz, u8p, u8p, u8p, ctypes.POINTER(ctypes.c_uint32), u8p, u8p]
         L.zg_last_sig_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.zg_equihash_verify.argtypes = [vp, ctypes.c_int, sz, u8p, sz, u8p, u8p, u8p]
         L.zg_headers_verify.argtypes = [vp, sz, u8p, ctypes.c_uint32, u8p, u8p, u8p]
@@ -195,7 +200,7 @@ def hsig(random_seed, nf0, nf1, pubkey):
 
 
 # zg_debug_field_mul operand sizes (5: a b mod 2^255 - 19, 6: (a + b 2^256) mod l: plain, canonical results)
-FIELD_BYTES = {0: 48, 1: 48, 2: 96, 3: 32, 4: 32, 5: 32, 6: 32}
+FIELD_BYTES = {0: 48, 1: 48, 2: 96, 3: 32, 4: 32, 5: 32, 6: 32, 7: 32, 8: 32}
 
 
 def debug_field_mul(field, a, b, device=0):
@@ -208,6 +213,26 @@ def debug_field_mul(field, a, b, device=0):
     if rc:
         raise ZgError(rc, "zg_debug_field_mul")
     return [out.raw[w * i:w * i + w] for i in range(n)]
+
+
+def pack_ecdsa(pubkeys, sigs, msgs):
+    """the buffers of zg_ecdsa_verify: (pubkeys n x 65 zero-padded, pubkey_len, sigs back to back, sig_off as
+    a ctypes uint32 array of n + 1, msg n x 32). A key longer than 255 bytes is sent as length 0 (any length
+    other than 33 or 65 is ECDSA_PUBLIC and its bytes are not read)"""
+    n = len(pubkeys)
+    if not (len(sigs) == len(msgs) == n and all(len(m) == 32 for m in msgs)):
+        raise ZgError(-1, "ecdsa_verify takes one signature and one 32-byte message per key")
+    lens = bytes(len(k) if len(k) <= 255 else 0 for k in pubkeys)
+    keys = b"".join(bytes(k)[:ECDSA_PUBKEY_STRIDE].ljust(ECDSA_PUBKEY_STRIDE, b"\0") for k in pubkeys)
+    off = (ctypes.c_uint32 * (n + 1))()
+    total = 0
+    for i, s in enumerate(sigs):
+        off[i] = total
+        total += len(s)
+    off[n] = total
+    if total >= 1 << 32:
+        raise ZgError(-1, "ecdsa_verify: the signatures exceed 4 GiB")
+    return keys, lens, b"".join(map(bytes, sigs)), off, b"".join(map(bytes, msgs))
 
 
 def pow_valid(max_bits, bits, hash32):
@@ -434,9 +459,19 @@ class Context:
         self._chk(lib().zg_headers_verify(self._p, n, b"".join(map(bytes, headers)), max_bits & 0xFFFFFFFF, st, hs, fl))
         return list(st.raw[:n]), [hs.raw[32 * i:32 * i + 32] for i in range(n)], list(fl.raw[:n])
 
+    def ecdsa_verify(self, pubkeys, sigs, msgs):
+        """per item: keys::Public::verify -- Public::from_slice of the key (33 or 65 bytes), Signature::from_der_lax
+        of the signature (DER without its hashtype byte, any length), verify over the 32-byte sighash -> list of
+        ECDSA_* statuses (0 ok, 1 public key, 2 signature encoding, 3 signature)"""
+        n = len(pubkeys)
+        keys, lens, sg, off, msg = pack_ecdsa(pubkeys, sigs, msgs)
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._chk(lib().zg_ecdsa_verify(self._p, n, keys, lens, sg + b"\0", off, msg, st))
+        return list(st.raw[:n])
+
     def last_sig_kernel_ms(self):
-        """device time of the kernel(s) of the last ed25519_verify / redjubjub_verify / equihash_verify /
-        headers_verify call"""
+        """device time of the kernel(s) of the last ed25519_verify / ecdsa_verify / redjubjub_verify /
+        equihash_verify / headers_verify call"""
         ms = ctypes.c_float(0)
         self._chk(lib().zg_last_sig_kernel_ms(self._p, ctypes.byref(ms)))
         return ms.value
