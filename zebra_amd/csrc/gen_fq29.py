@@ -344,6 +344,81 @@ def main():
     o += fn("fq29d_to_mont", "uint32_t* r, const uint32_t* a", body,
             ["14-digit a R' (< 2p) -> canonical 12-word a R"])
 
+    # ---- digit-resident Fq2 (zg_fqd.h Fq2D; the lane R-chain of zg_lines.h): two interleaved
+    # reductions by 2^406, digits in and out. A column holds 14 terms of each product and 14 m*p
+    # terms (< 2^58 each), so the digit bounds of the operands must keep
+    #   14 (sum over the column's products of max digit x max digit) + 14 2^58 < 2^64.
+    body = redc_full([("r0", "a0", lambda k: terms("a", "b", k)), ("r1", "a1", lambda k: terms("c", "d", k))])
+    o += fn("fq29d_mul2", "uint32_t* r0, uint32_t* r1, const uint32_t* a, const uint32_t* b, const uint32_t* c, "
+            "const uint32_t* d", body,
+            ["r0 = a b 2^-406, r1 = c d 2^-406 mod p in digits, the two chains interleaved (an Fq2 square as",
+             "(x0 + x1)(x0 - x1), x0 (2 x1); an Fq2 times an Fq). Digit bounds: max(a) max(b) < 3.5 2^58, same",
+             "for c d (one operand may hold unnormalized digits < 2^30). Outputs normalized, < a b / 2^406 + p."])
+    body = redc_full([("c0", "a0", lambda k: terms("x0", "y0", k) + terms("x1", "n1", k)),
+                      ("c1", "a1", lambda k: terms("x0", "y1", k) + terms("x1", "y0", k))])
+    o += fn("f2d_mul29", "uint32_t* c0, uint32_t* c1, const uint32_t* x0, const uint32_t* x1, const uint32_t* y0, "
+            "const uint32_t* y1, const uint32_t* n1", body,
+            ["Fq2 product in digits, schoolbook with two reductions (the MAC structure of f2_mul29):",
+             "  c0 = REDC'(x0 y0 + x1 n1),  c1 = REDC'(x0 y1 + x1 y0),  n1 = k p - y1 digit-wise (>= 0).",
+             "x, y normalized (digits < 2^29), n1 digits < 2^30: 14 (2^58 + 2^59) + 14 2^58 < 2^64."])
+    body = ["  uint32_t t[12];"]
+    for w in range(12):
+        b_ = 32 * w
+        L, o_ = b_ // W, b_ % W
+        parts = ["(u[%d] >> %d)" % (L, o_) if o_ else "u[%d]" % L, "(u[%d] << %d)" % (L + 1, W - o_)]
+        if o_ + 32 > 2 * W:
+            parts.append("(u[%d] << %d)" % (L + 2, 2 * W - o_))
+        body.append("  t[%d] = %s;" % (w, " | ".join(parts)))
+    body.append("  fq29_canon(r, t);")
+    o += fn("fq29d_pack", "uint32_t* r, const uint32_t* u", body,
+            ["14 normalized digits of a value < 2p -> its canonical 12 words (the repack and conditional",
+             "subtraction that close fq29_mul)"])
+    for (nm, sh, doc) in (("fq29d_split", 0, "12 words -> 14 digits of the same value"),
+                          ("fq29d_split22", 22, "12 words a -> 14 digits of 2^22 a (a R -> a R' = 2^406, "
+                                                "unreduced: < 2^22 p for canonical a)")):
+        body = []
+        for L in range(D):
+            s_ = W * L - sh
+            if s_ < 0:
+                body.append("  d[%d] = (a[0] << %d) & FQ29_MASK;" % (L, -s_))
+                continue
+            w, o_ = s_ >> 5, s_ & 31
+            if o_ + W <= 32:
+                e = "a[%d]" % w if o_ == 0 else "(a[%d] >> %d)" % (w, o_)
+                if o_ + W < 32:
+                    e += " & FQ29_MASK"
+            elif w + 1 < 12:
+                e = "zg_alignbit(a[%d], a[%d], %d) & FQ29_MASK" % (w + 1, w, o_)
+            else:
+                e = "a[%d] >> %d" % (w, o_)
+            body.append("  d[%d] = %s;" % (L, e))
+            if w + 1 >= 12 and o_ + W > 32:
+                body.append("  zg_opaque(d[%d]);  // narrow top digit: see gen_mont29" % L)
+        o += fn(nm, "uint32_t* d, const uint32_t* a", body, [doc])
+    # a 2^-22 mod p: one Montgomery step with a 22-bit digit (14 m*p products instead of the 392 of
+    # fq29d_to_mont), then the repack from bit 22 and the conditional subtraction
+    pinv22 = PINV & ((1 << 22) - 1)
+    assert (P * pinv22 + 1) % (1 << 22) == 0
+    body = ["  uint32_t u[14], t[12];", "  uint32_t m = (a[0] * 0x%08xu) & 0x3fffffu;" % pinv22, "  zg_opaque(m);",
+            "  uint64_t acc = 0;"]
+    for k in range(D):
+        body.append("  acc += a[%d];" % k)
+        body.append("  acc += (uint64_t)m * 0x%08xu;" % P29[k])
+        body.append("  u[%d] = (uint32_t)acc%s;" % (k, " & FQ29_MASK" if k < D - 1 else ""))
+        if k < D - 1:
+            body.append("  acc >>= 29;")
+    for w in range(12):
+        b_ = 22 + 32 * w
+        L, o_ = b_ // W, b_ % W
+        parts = ["(u[%d] >> %d)" % (L, o_) if o_ else "u[%d]" % L, "(u[%d] << %d)" % (L + 1, W - o_)]
+        if o_ + 32 > 2 * W and L + 2 < D:
+            parts.append("(u[%d] << %d)" % (L + 2, 2 * W - o_))
+        body.append("  t[%d] = %s;" % (w, " | ".join(parts)))
+    body.append("  fq29_canon(r, t);")
+    o += fn("fq29d_red22", "uint32_t* r, const uint32_t* a", body,
+            ["14-digit a R' (normalized, any value < 2^22 p) -> canonical 12-word a R: (a + m p) / 2^22 with",
+             "m = -a / p mod 2^22, < 2p before the conditional subtraction"])
+
     # ---- the 256-bit moduli: BLS12-381 Fr (Jubjub base field) and BN254 Fq (PGHR13)
     R_BLS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
     P_BN = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47

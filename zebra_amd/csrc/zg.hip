@@ -189,6 +189,8 @@ struct zg_ctx {
                              // round 6), 0 the fused Q4 / Q4SQ programs (same values)
   int lp_parts = 0;          // ZG_LINE_PROD_PARTS: step parts overlapping line products and chains: 1..8 equal
                              // parts, 0 (default) wave-aligned parts (lineprod_parts)
+  int glv_lds = ZG_DEC_GLV_LDS;  // ZG_DEC_GLV_LDS: decode's r_i A_i two columns per step from an LDS table, in a
+                             // launch of its own (K4 layout only; zg_decode.h)
   int pairs_late = 0;        // ZG_PAIRS_LATE=1: with group line products, the root's VK MSM + pairs go on the side
                              // stream AFTER the group chains instead of before them (round 6, r06f: 8k with line
                              // products 2.88 -> 2.77 ms per batch, still behind the quad chain's 2.61; 16k 4.19 ->
@@ -348,6 +350,7 @@ extern "C" zg_ctx* zg_create(const zg_config* cfg) {
   if (ctx->lines_affine_xl) ctx->lines_affine = 4;
   if (const char* e = getenv("ZG_LINE_PROD_PARTS")) ctx->lp_parts = std::max(1, std::min(ZG_LP_PARTS_MAX, atoi(e)));
   if (const char* e = getenv("ZG_PAIRS_LATE")) ctx->pairs_late = atoi(e) ? 1 : 0;
+  if (const char* e = getenv("ZG_DEC_GLV_LDS")) ctx->glv_lds = atoi(e) ? 1 : 0;
   if (ctx->line_group != -1 && (ctx->line_group < 4 || (ctx->line_group & (ctx->line_group - 1)))) ctx->line_group = 0;
   if (const char* e = getenv("ZG_K4_MIN")) ctx->k4_min = atol(e);
   if (const char* e = getenv("ZG_FCHAIN_SINGLE")) ctx->singles = atoi(e);
@@ -767,7 +770,7 @@ static int launch_node_msm_pairs(zg_ctx* ctx, const BatchBufs& b, const NodeBufs
 }
 
 namespace zg {
-hipError_t launch_batch_decode(unsigned groups, hipStream_t st, const BatchBufs& b, int cglv);  // zg_decode.hip
+hipError_t launch_batch_decode(unsigned groups, hipStream_t st, const BatchBufs& b, int cglv, int glv_lds);  // zg_decode.hip
 hipError_t launch_msm_root(hipStream_t st, const BatchBufs& b, MsmBufs m, const int* gate, hipEvent_t bucket0,
                            hipEvent_t bucket1, int k4, bool alone);                                       // zg_msm.hip
 hipError_t launch_c_leaves(hipStream_t st, const BatchBufs& b);                                // zg_msm.hip
@@ -875,7 +878,7 @@ static int run_pipeline(zg_ctx* ctx) {
   const bool alone = ctx->dev->inflight.load(std::memory_order_relaxed) == 0;
   const int k4 = (long)ctx->npad >= ctx->k4_min || !alone ? 1 : 0;
   ctx->k4_last = k4;
-  HIPCHK(launch_batch_decode(dgroups, ctx->stream, b, !k4));
+  HIPCHK(launch_batch_decode(dgroups, ctx->stream, b, !k4, ctx->glv_lds));
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   ctx->trees_built = 0;
   ctx->c_tree_pending = 0;

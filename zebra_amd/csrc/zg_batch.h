@@ -5,6 +5,12 @@
 #include "zg_groth16.h"
 #include "zg_prog.h"
 
+// ZG_DEC_GLV_LDS: the default of the context's glv_lds (zg_decode.h k_decode_glv_lds); a compile-time
+// switch for A/B builds of zg.hip, overridden per context by ZG_DEC_GLV_LDS in the environment
+#ifndef ZG_DEC_GLV_LDS
+#define ZG_DEC_GLV_LDS 0
+#endif
+
 namespace zg {
 
 #define ZG_MSM_SLOTS (ZG_MAX_IC + 1)  // ic terms + the alpha term

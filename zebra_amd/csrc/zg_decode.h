@@ -66,7 +66,49 @@ __global__ void __launch_bounds__(64, ZG_DECODE_SQRT_WPE) k_decode_sqrt(BatchBuf
 }
 #else
 
-// JOB < 0: every job in one launch (grid 4G, the product's only launch); JOB = 0 / 1 / 2: that job
+// ZG_DEC_GLV_LDS (default 0; ZG_DEC_GLV_LDS in the environment of zg_create overrides): on the K4
+// layout (cglv = 0) the products r_i A_i run two columns per step from a table in LDS
+// (g1_glv_mul_w2_t with GlvTabLds, 32 mixed additions fewer) in a launch of their own,
+// k_decode_glv_lds, followed by k_decode_points<-2> for the other jobs: static LDS applies to every
+// block of a launch, and the table is 8 x 2 x 14 x 64 words = 56 KB, so only two such blocks fit a
+// CU (one wave per two SIMDs, against two per SIMD for the one-column form). Measured: DESIGN.md 4e.
+// (the default is defined in zg_batch.h, which zg.hip sees too)
+#if ZG_DECODE_FQD
+struct GlvTabLds {
+  uint32_t* base;  // the block's table + lane: [entry][coordinate][digit][lane]
+  __device__ __forceinline__ void put(int e, int c, const FqD& v) const {
+#pragma unroll
+    for (int d = 0; d < 14; d++) base[((e * 2 + c) * 14 + d) * 64] = v.d[d];
+  }
+  __device__ __forceinline__ FqD get(int e, int c) const {
+    FqD v;
+#pragma unroll
+    for (int d = 0; d < 14; d++) v.d[d] = base[((e * 2 + c) * 14 + d) * 64];
+    return v;
+  }
+};
+// lane = proof: [r_i] A_i -> ptA (affine), as blocks [0, G) of k_decode_points do
+__global__ void __launch_bounds__(64, ZG_DECODE_WPE) k_decode_glv_lds(BatchBufs b) {
+  __shared__ uint32_t lds_tab[8 * 2 * 14 * 64];
+  const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (i >= b.npad) return;
+  const G1A p = b.ptAC[i];
+  G1A o;
+  o.inf = true;
+  if (!p.inf) {
+    uint64_t ra, rb;
+    batch_scalar_ab(b.r + (size_t)i * 16, &ra, &rb);
+    const GlvTabLds tab{lds_tab + (threadIdx.x & 63)};
+    G1J j;
+    g1_glv_mul_w2_t(&j, &p, ra, rb, tab);
+    o = jac_to_aff(j);
+  }
+  b.ptA[i] = o;
+}
+#endif
+
+// JOB < 0: every job in one launch (grid 4G, the product's only launch; JOB = -2: every job but the
+// GLV products of the K4 layout, grid 3G, after k_decode_glv_lds); JOB = 0 / 1 / 2: that job
 // alone (grid G / 2G / G: round 4's per-job profiles, profiles/r04b_kernel_stats_decode_split.csv,
 // compiled only by tooling)
 // cglv (small shards, ZG_K4_MIN): the GLV products r_i C_i run here too, as blocks [G, 2G) beside
@@ -76,7 +118,7 @@ __global__ void __launch_bounds__(64, ZG_DECODE_SQRT_WPE) k_decode_sqrt(BatchBuf
 template <int JOB>
 __global__ void __launch_bounds__(64, ZG_DECODE_WPE) k_decode_points(BatchBufs b, int cglv) {
   const int G = (b.npad + 63) / 64, nglv = cglv ? 2 * G : G;
-  const int blk = JOB < 0 ? (int)blockIdx.x : JOB == 0 ? (int)blockIdx.x : JOB == 1 ? nglv + (int)blockIdx.x
+  const int blk = JOB == -2 ? nglv + (int)blockIdx.x : JOB <= 0 ? (int)blockIdx.x : JOB == 1 ? nglv + (int)blockIdx.x
                                                                                      : nglv + 2 * G + (int)blockIdx.x;
   // 0 GLV (A, or C from block G on), 1 subgroup, 2 B (wave-uniform)
   const int job = JOB >= 0 ? JOB : blk < nglv ? 0 : blk < nglv + 2 * G ? 1 : 2;

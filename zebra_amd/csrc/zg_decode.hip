@@ -19,11 +19,18 @@ namespace zg {
 hipError_t launch_decode_sqrt(unsigned groups, hipStream_t st, const BatchBufs& b);  // zg_decode_sqrt.hip
 
 // G1 square roots, then the point jobs (GLV r_i A_i, subgroup checks, B), then per-proof statuses and Fr leaves
-hipError_t launch_batch_decode(unsigned groups, hipStream_t st, const BatchBufs& b, int cglv) {
+// glv_lds: on the K4 layout, the GLV products from an LDS table in a launch of their own (ZG_DEC_GLV_LDS)
+hipError_t launch_batch_decode(unsigned groups, hipStream_t st, const BatchBufs& b, int cglv, int glv_lds) {
   const hipError_t e = launch_decode_sqrt(groups, st, b);
   if (e != hipSuccess) return e;
   const unsigned nglv = cglv ? 2 * groups : groups;
-  hipLaunchKernelGGL(k_decode_points<-1>, dim3(nglv + 3 * groups), dim3(64), 0, st, b, cglv);
+#if ZG_DECODE_FQD
+  if (glv_lds && !cglv) {
+    hipLaunchKernelGGL(k_decode_glv_lds, dim3(groups), dim3(64), 0, st, b);
+    hipLaunchKernelGGL(k_decode_points<-2>, dim3(3 * groups), dim3(64), 0, st, b, 0);
+  } else
+#endif
+    hipLaunchKernelGGL(k_decode_points<-1>, dim3(nglv + 3 * groups), dim3(64), 0, st, b, cglv);
   hipLaunchKernelGGL(k_decode_finish, dim3(groups), dim3(64), 0, st, b);
   return hipGetLastError();
 }

@@ -211,6 +211,171 @@ ZG_INL Fq fqd_to(const FqD& a) {
   return r;
 }
 
+// ------------------------------------------------------------------ bound checking (host only)
+// A build with ZG_FQD_CHECK verifies every FQD_CHK(v, K) on the host: v's digits 0..12 are
+// normalized and v < K p. Violations are counted (fqd_check_fails()), never on the device.
+#if defined(ZG_FQD_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+inline int& fqd_check_fails() {
+  static int n = 0;
+  return n;
+}
+inline void fqd_check(const FqD& v, uint32_t K) {
+  const FqDK kp = fqd_kp(K, 0);
+  bool ok = true, lt = false;
+  for (int i = 0; i < 13; i++) ok = ok && v.d[i] <= FQ29_MASK;
+  for (int i = 13; i >= 0 && !lt; i--) {
+    if (v.d[i] > kp.d[i]) break;
+    lt = v.d[i] < kp.d[i];
+  }
+  if (!ok || !lt) fqd_check_fails()++;
+}
+#define FQD_CHK(v, K) fqd_check(v, K)
+#else
+#define FQD_CHK(v, K) ((void)0)
+#endif
+
+// ------------------------------------------------------------------ Fq2 = Fq[u] / (u^2 + 1) in lazy digits
+// Fq2D holds both coefficients as FqD (R' = 2^406, normalized digits, value below a tracked K p).
+// The products are schoolbook with one reduction per coefficient (the MAC structure of f2_mul29 /
+// f2_sqr29 / f2_mul_fq29 of zg_fq29_gen.h, without their splits, repacks and canonicalisation):
+//   value: an output is < S / 2^406 + p for its column sum S, so < 2p whenever S < 2^25 p^2;
+//   digits: an operand pair may have one side unnormalized (digits < 2^30), see fq29d_mul2.
+// Mixed representations cost nothing: REDC' of an R' operand (x 2^406) and an R operand (x 2^384, the
+// word form's digits as they are) is the product in R form, i.e. the word form's Montgomery value,
+// and a canonical word-form value shifted left by 22 bits is its R' form below 2^22 p.
+struct Fq2D {
+  FqD c0, c1;
+};
+#define F2D_CHK(v, K) (FQD_CHK((v).c0, K), FQD_CHK((v).c1, K))
+
+ZG_INL Fq2D f2d_one() { return {fqd_one(), fqd_zero()}; }
+ZG_INL Fq2D f2d_from(const Fq2& a) { return {fqd_from(a.c0), fqd_from(a.c1)}; }
+ZG_INL Fq2D f2d_add(const Fq2D& a, const Fq2D& b) { return {fqd_add(a.c0, b.c0), fqd_add(a.c1, b.c1)}; }
+template <int C>
+ZG_INL Fq2D f2d_smul(const Fq2D& a) {
+  return {fqd_smul<C>(a.c0), fqd_smul<C>(a.c1)};
+}
+template <int K, int CA, int CB>
+ZG_INL Fq2D f2d_sub(const Fq2D& a, const Fq2D& b) {
+  return {fqd_sub<K, CA, CB>(a.c0, b.c0), fqd_sub<K, CA, CB>(a.c1, b.c1)};
+}
+template <int K>
+ZG_INL Fq2D f2d_sub2(const Fq2D& a, const Fq2D& b, const Fq2D& c) {
+  return {fqd_sub2<K>(a.c0, b.c0, c.c0), fqd_sub2<K>(a.c1, b.c1, c.c1)};
+}
+// the 32-bit budget of a digit-wise sum before fqd_norm: digit i holds at most kp_i plus ca normalized
+// digits, plus the carry out of digit i - 1 (below 8 when that digit stayed below 2^32)
+constexpr bool fqd_budget_ok(const FqDK& kp, uint32_t ca) {
+  for (int i = 0; i < 14; i++)
+    if ((uint64_t)kp.d[i] + (uint64_t)ca * FQ29_MASK + (i > 0 ? 7u : 0u) > 0xffffffffull) return false;
+  return true;
+}
+// a - b - c - 4d + K p   (requires b + c + 4d <= (K - 1) p; result < a + K p). The budget is exactly
+// full: a borrowed digit of K p is at most 2^29 - 1 + 6 2^29 - 6, a adds at most 2^29 - 1 (2^32 - 8),
+// and the carry into it is at most 7; digit 0 (not lowered by 6) takes no carry.
+template <int K>
+ZG_INL FqD fqd_sub114(const FqD& a, const FqD& b, const FqD& c, const FqD& d) {
+  constexpr FqDK kp = fqd_kp(K, 6);
+  static_assert(fqd_budget_ok(kp, 1), "digit budget");
+  FqD r;
+#pragma unroll
+  for (int i = 0; i < 14; i++) r.d[i] = a.d[i] + (kp.d[i] - b.d[i] - c.d[i] - 4u * d.d[i]);
+  fqd_norm(r.d);
+  return r;
+}
+// Unnormalized forms for a product's scalar-side operand (digits < 3 2^29): 2a, and K p - 2a
+// (requires 2a <= (K - 1) p; value < K p)
+ZG_INL Fq2D f2d_dbl_raw(const Fq2D& a) {
+  Fq2D r;
+#pragma unroll
+  for (int i = 0; i < 14; i++) {
+    r.c0.d[i] = 2u * a.c0.d[i];
+    r.c1.d[i] = 2u * a.c1.d[i];
+  }
+  return r;
+}
+template <int K>
+ZG_INL Fq2D f2d_negdbl_raw(const Fq2D& a) {
+  constexpr FqDK kp = fqd_kp(K, 2);
+  Fq2D r;
+#pragma unroll
+  for (int i = 0; i < 14; i++) {
+    r.c0.d[i] = kp.d[i] - 2u * a.c0.d[i];
+    r.c1.d[i] = kp.d[i] - 2u * a.c1.d[i];
+  }
+  return r;
+}
+
+// x y for x, y normalized, y.c1 <= (KY - 1) p: < 2p per coefficient for |x| (|y| + KY) < 2^24 (in units of p)
+template <int KY>
+ZG_INL Fq2D f2d_mul(const Fq2D& x, const Fq2D& y) {
+  constexpr FqDK kp = fqd_kp(KY, 1);
+  uint32_t n1[14];
+#pragma unroll
+  for (int i = 0; i < 14; i++) n1[i] = kp.d[i] - y.c1.d[i];
+  Fq2D r;
+  f2d_mul29(r.c0.d, r.c1.d, x.c0.d, x.c1.d, y.c0.d, y.c1.d, n1);
+  return r;
+}
+// a^2 for a normalized, a.c1 <= (K - 1) p: c0 = (a0 + a1)(a0 - a1 + K p), c1 = a0 (2 a1); < 2p
+template <int K>
+ZG_INL Fq2D f2d_sqr(const Fq2D& a) {
+  const FqD dif = fqd_sub<K, 1, 1>(a.c0, a.c1);
+  uint32_t s[14], t[14];
+#pragma unroll
+  for (int i = 0; i < 14; i++) {
+    s[i] = a.c0.d[i] + a.c1.d[i];
+    t[i] = a.c1.d[i] << 1;
+  }
+  Fq2D r;
+  fq29d_mul2(r.c0.d, r.c1.d, s, dif.d, a.c0.d, t);
+  return r;
+}
+// x q for a canonical word-form q (a G2 coordinate read from memory), result in R' digits:
+// q enters as 2^22 q (< 2^22 p), so the result is < (|x| 2^23 / 2^25 + 1) p
+ZG_INL Fq2D f2d_mul_w22(const Fq2D& x, const Fq2& q) {
+  const Fq nq1 = fq_neg(q.c1);
+  uint32_t y0[14], y1[14], n1[14];
+  fq29d_split22(y0, q.c0.l);
+  fq29d_split22(y1, q.c1.l);
+  fq29d_split22(n1, nq1.l);
+  Fq2D r;
+  f2d_mul29(r.c0.d, r.c1.d, x.c0.d, x.c1.d, y0, y1, n1);
+  return r;
+}
+// x q for a canonical word-form q, result in the canonical word form (x R' times q R is x q R)
+ZG_INL Fq2 f2d_mul_to_w(const Fq2D& x, const Fq2& q) {
+  constexpr FqDK kp = fqd_kp(2, 1);
+  uint32_t y0[14], y1[14], n1[14], u0[14], u1[14];
+  fq29d_split(y0, q.c0.l);
+  fq29d_split(y1, q.c1.l);
+#pragma unroll
+  for (int i = 0; i < 14; i++) n1[i] = kp.d[i] - y1[i];
+  f2d_mul29(u0, u1, x.c0.d, x.c1.d, y0, y1, n1);
+  Fq2 r;
+  fq29d_pack(r.c0.l, u0);
+  fq29d_pack(r.c1.l, u1);
+  return r;
+}
+// (x0 s, x1 s) for a canonical word-form s, result in the canonical word form; x may be
+// unnormalized (digits < 3 2^29), |x| < 2^24
+ZG_INL Fq2 f2d_mulfq_to_w(const Fq2D& x, const Fq& s) {
+  uint32_t sd[14], u0[14], u1[14];
+  fq29d_split(sd, s.l);
+  fq29d_mul2(u0, u1, x.c0.d, sd, x.c1.d, sd);
+  Fq2 r;
+  fq29d_pack(r.c0.l, u0);
+  fq29d_pack(r.c1.l, u1);
+  return r;
+}
+// R' digits (normalized, < 2^22 p) -> the canonical word form
+ZG_INL Fq2 f2d_to_w(const Fq2D& a) {
+  Fq2 r;
+  fq29d_red22(r.c0.l, a.c0.d);
+  fq29d_red22(r.c1.l, a.c1.d);
+  return r;
+}
+
 // ------------------------------------------------------------------ G1 Jacobian (y^2 = x^3 + 4)
 // Invariant of every G1D below: X < 35p, Y < 19p, Z < 4p; infinity is Z == 0 mod p.
 struct G1D {

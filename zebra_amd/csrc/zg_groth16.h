@@ -172,8 +172,18 @@ ZG_INL G1J g1_glv_mul_d(const G1A& p, uint64_t a, uint64_t b) {
 // E = 2 (P + e_j sigma P) + r (P + e_{j-1} sigma P), r = +-1 -- eight affine entries built once
 // (one doubling, five mixed additions, one batched inversion; sigma(X, Y, Z) = (beta X, Y, Z) and
 // 3P + 3 sigma P = -sigma^2(3P) come free), then 64 doublings and 32 mixed additions instead of
-// 64 + 64. The table is indexed per lane (private memory): 8 x 2 FqD.
-ZG_NOINL inline void g1_glv_mul_w2_p(G1J* out, const G1A* pp, uint64_t a, uint64_t b) {
+// 64 + 64. The table lives in a store Tab (put / get of entry 0..7, coordinate 0 = x, 1 = y), as
+// the R-chain's state lives in St (zg_lines.h): GlvTabHost is a plain per-lane array (on the device
+// that is the private segment, gathered with a different index per lane: 2.1 GB of HBM traffic per
+// 64k launch); GlvTabLds (zg_decode.h) is LDS laid out [entry][coordinate][digit][lane],
+// where the bank depends on the lane alone and a per-lane entry index costs nothing.
+struct GlvTabHost {
+  FqD t[8][2];
+  ZG_HD void put(int e, int c, const FqD& v) { t[e][c] = v; }
+  ZG_HD FqD get(int e, int c) const { return t[e][c]; }
+};
+template <class Tab>
+ZG_INL void g1_glv_mul_w2_t(G1J* out, const G1A* pp, uint64_t a, uint64_t b, Tab& tab) {
   const FqD px = fqd_from(pp->x), py = fqd_from(pp->y);
   const FqD be = fqd_from(fq_const(G1_BETA)), be2 = fqd_from(fq_const(G1_BETA2));
   const FqD sx = fqd_mul(px, be), s2x = fqd_mul(px, be2), ny = fqd_neg2(py);  // sigma P x, sigma^2 P x, -y
@@ -191,7 +201,6 @@ ZG_NOINL inline void g1_glv_mul_w2_p(G1J* out, const G1A* pp, uint64_t a, uint64
   c[0] = J[0].z;
   for (int k = 1; k < 5; k++) c[k] = fqd_mul(c[k - 1], J[k].z);
   FqD inv = fqd_from(fq_inv(fqd_to(c[4])));
-  FqD tx[8], ty[8];
   for (int k = 4; k >= 0; k--) {
     const FqD zi = k ? fqd_mul(inv, c[k - 1]) : inv;
     if (k) inv = fqd_mul(inv, J[k].z);
@@ -199,17 +208,17 @@ ZG_NOINL inline void g1_glv_mul_w2_p(G1J* out, const G1A* pp, uint64_t a, uint64
     const FqD x = fqd_mul(J[k].x, zi2), y = fqd_mul(J[k].y, fqd_mul(zi2, zi));
     // entry index (e_j << 2) | (e_{j-1} << 1) | (r == -1)
     const int idx = k == 0 ? 0 : k == 1 ? 2 : k == 2 ? 4 : k == 3 ? 3 : 5;
-    tx[idx] = x;
-    ty[idx] = y;
+    tab.put(idx, 0, x);
+    tab.put(idx, 1, y);
     if (k == 0) {  // 3P + 3 sigma P = -sigma^2(3P)
-      tx[6] = fqd_mul(x, be2);
-      ty[6] = fqd_neg2(y);
+      tab.put(6, 0, fqd_mul(x, be2));
+      tab.put(6, 1, fqd_neg2(y));
     }
   }
-  tx[1] = px;   // P
-  ty[1] = py;
-  tx[7] = s2x;  // P + sigma P = (beta^2 x, -y)
-  ty[7] = ny;
+  tab.put(1, 0, px);   // P
+  tab.put(1, 1, py);
+  tab.put(7, 0, s2x);  // P + sigma P = (beta^2 x, -y)
+  tab.put(7, 1, ny);
   // the sign-aligned recoding of g1_glv_mul_d_p: k0 = 2a + 1 = sum s_j 2^j, s_j = +-1 (s_64 = +1)
   uint64_t k1 = b, e = 0;
   for (int j = 0; j < 64; j++) {
@@ -224,10 +233,14 @@ ZG_NOINL inline void g1_glv_mul_w2_p(G1J* out, const G1A* pp, uint64_t a, uint64
     const uint32_t ej = (e >> j) & 1u, el = (e >> (j - 1)) & 1u;
     const uint32_t sj = (a >> j) & 1u, sl = (a >> (j - 1)) & 1u;  // 1: s = +1
     const int idx = (int)((ej << 2) | (el << 1) | (sj ^ sl));
-    const FqD y = ty[idx];
-    q = g1d_add_aff(g1d_dbl(g1d_dbl(q)), tx[idx], sj ? y : fqd_sub<4, 0, 1>(fqd_zero(), y));  // -y < 4p
+    const FqD y = tab.get(idx, 1);
+    q = g1d_add_aff(g1d_dbl(g1d_dbl(q)), tab.get(idx, 0), sj ? y : fqd_sub<4, 0, 1>(fqd_zero(), y));  // -y < 4p
   }
   *out = g1d_to_jac(q);
+}
+ZG_NOINL inline void g1_glv_mul_w2_p(G1J* out, const G1A* pp, uint64_t a, uint64_t b) {
+  GlvTabHost tab;
+  g1_glv_mul_w2_t(out, pp, a, b, tab);
 }
 ZG_INL G1J g1_glv_mul_w2(const G1A& p, uint64_t a, uint64_t b) {
   G1J r;

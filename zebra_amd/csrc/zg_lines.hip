@@ -7,14 +7,52 @@
 // (c2, c1 px, c0 py) = (A, B, C) to lines[n][proof] for the f-chain. The last point is [x] B,
 // so the G2 subgroup check of B (psi(B) = [u] B) closes the kernel. Same values as the staged
 // program k_batch_lines (zg_kernels.h: lane = proof, wave = product, LDS atoms, a barrier per
-// round): here every lane runs its proof's products back to back in registers, no LDS, no
-// barriers, two waves per SIMD -- the issue pattern of the decode kernels.
+// round): here every lane runs its proof's products back to back, the running point in the
+// lane's own LDS rows, no barriers, two waves per SIMD -- the issue pattern of the decode kernels.
+// ZG_LINES_FQD (zg_lines.h, default 1): the chain in lazy 29-bit digits (lsd_double / lsd_add).
 #include <hip/hip_runtime.h>
 
 #include "../../include/zg.h"
 #include "zg_lines.h"
 
 namespace zg {
+
+// The digit chain's state store: a coordinate's 26 packed words (LinesPackD) as 13 lane-contiguous
+// rows of uint2 (64 x 8 B per row: conflict-free ds_read_b64 / ds_write_b64), base already offset
+// by the lane. 3 x 13 x 512 B = 19.5 KB per block, so eight blocks (two waves per SIMD) fit a CU's
+// 160 KB; three unpacked 28-word coordinates (21 KB) would not.
+struct LinesLdsD {
+  static constexpr int ROWS = 13;
+  uint2* base;
+  __device__ __forceinline__ Fq2D get(int i) const {
+    const uint2* p = base + (size_t)i * ROWS * 64;
+    LinesPackD v;
+#pragma unroll
+    for (int q = 0; q < ROWS; q++) {
+      const uint2 r = p[q * 64];
+      v.w[2 * q] = r.x;
+      v.w[2 * q + 1] = r.y;
+    }
+    return lsd_unpack(v);
+  }
+  __device__ __forceinline__ void put(int i, const Fq2D& x) const {
+    uint2* p = base + (size_t)i * ROWS * 64;
+    const LinesPackD v = lsd_pack(x);
+#pragma unroll
+    for (int q = 0; q < ROWS; q++) p[q * 64] = make_uint2(v.w[2 * q], v.w[2 * q + 1]);
+  }
+  // one coefficient (words 13 coef .. 13 coef + 12 of the coordinate)
+  __device__ __forceinline__ void put1(int i, int coef, const FqD& x) const {
+    uint32_t* p = reinterpret_cast<uint32_t*>(base + (size_t)i * ROWS * 64);
+    uint32_t w[13];
+    lsd_pack1(w, x);
+#pragma unroll
+    for (int k = 0; k < 13; k++) {
+      const int j = 13 * coef + k;  // word j: row j / 2, component j % 2
+      p[(j >> 1) * 128 + (j & 1)] = w[k];
+    }
+  }
+};
 
 template <int WPE>
 __global__ void __launch_bounds__(64, WPE) k_batch_lines_lane(BatchBufs b, Fq2* lines) {
@@ -26,6 +64,17 @@ __global__ void __launch_bounds__(64, WPE) k_batch_lines_lane(BatchBufs b, Fq2* 
   // point and one step's temporaries
   const G2A* pq = &b.ptB[chk ? proof : 0];
   const G1A* pa = &b.ptA[act ? proof : 0];
+  int n = 0;
+#if ZG_LINES_FQD
+  __shared__ uint2 lds_pt[3 * LinesLdsD::ROWS * 64];  // X, Y, Z of the block's 64 proofs in digits (19.5 KB)
+  LinesLdsD st{lds_pt + (threadIdx.x & 63)};
+  lsd_init(st, pq, chk);
+  for (int i = ZG_XH_TOP; i >= -1; i--) {
+    lsd_double(st, pa, lines + ((size_t)(n++) * b.npad + proof) * 3, act);
+    if (i >= 0 && ((ZG_XH >> i) & 1ull)) lsd_add(st, pq, pa, lines + ((size_t)(n++) * b.npad + proof) * 3, act && chk);
+  }
+  const G2J r = lsd_result(st);
+#else
   __shared__ uint4 lds_pt[3 * ZG_ATOM_ROWS * 64];  // X, Y, Z of the block's 64 proofs (18 KB)
   AtomSpace st{lds_pt};
   if (chk) {
@@ -36,19 +85,15 @@ __global__ void __launch_bounds__(64, WPE) k_batch_lines_lane(BatchBufs b, Fq2* 
     st.put(1, f2_one());
   }
   st.put(2, f2_one());
-  int n = 0;
   for (int i = ZG_XH_TOP; i >= -1; i--) {
     ls_double(st, pa, lines + ((size_t)(n++) * b.npad + proof) * 3, act);
     if (i >= 0 && ((ZG_XH >> i) & 1ull)) ls_add(st, pq, pa, lines + ((size_t)(n++) * b.npad + proof) * 3, act && chk);
   }
   const G2J r = {st.get(0), st.get(1), st.get(2)};
-  // r = [x] B (Jacobian). B in G2  <=>  psi(B) = [u] B = -[x] B  <=>  X = psi_x Z^2, Y = -psi_y Z^3,
-  // Z != 0 (the step formulas are exact unless they degenerate, which only a B outside G2 can
-  // make happen, and then Z = 0)
+#endif
+  // r = [x] B (Jacobian, canonical): the G2 subgroup check of B closes the kernel (ls_in_g2)
   if (chk) {
-    const G2A s = g2_psi(*pq);
-    const Fq2 z2 = ls_sqr(r.z), z3 = ls_mul(z2, r.z);
-    const bool in_g2 = !f2_is_zero(r.z) && f2_eq(r.x, ls_mul(s.x, z2)) && f2_eq(r.y, f2_neg(ls_mul(s.y, z3)));
+    const bool in_g2 = ls_in_g2(r, *pq);
     if (!in_g2) {
       atomicAdd(b.bfail, 1);
       b.status[proof] = ST_DECODE_INVALID;
