@@ -388,10 +388,20 @@ int zg_tree_roots_device(zg_ctx* ctx, int kind, int height, const uint8_t* state
  *        (-> ErrorKind::InvalidEncoding), ZG_STATUS_VERIFY_FAILED (-> InvalidPGHRProof),
  *        ZG_STATUS_INPUT_NONCANONICAL (an input >= r: not constructible as bn::Fr). The five
  *        pairing equalities of a proof are checked as one product with OS-random 128-bit weights
- *        (false accept ~2^-128). One batch check per chunk of at most 65,536 proofs (the
- *        call's device scratch stays bounded however large n is). kernel_ms optional: device
+ *        (false accept ~2^-128). One batch check per chunk of at most 65,536 proofs (fewer
+ *        with ZG_PGHR_CHUNK, see zg_pghr13_shape; the call's device scratch stays bounded
+ *        however large n is). kernel_ms optional: device
  *        time of the kernels, summed over the chunks. A key is freed from the device cache once
  *        no context points at it (a context that loads another key, or is destroyed).
+ *   zg_pghr13_shape (tests, tools; host only, launches nothing): what a zg_pghr13_verify call of n
+ *        proofs on this context would launch, from the same helper the call itself uses: chunk =
+ *        proofs per batch check (ZG_PGHR_CHUNK in the environment at zg_create, 64..65,536, default
+ *        65,536); of the call's first chunk, min(n, chunk) proofs: straus_b = proofs per lane of the
+ *        key pairs' Straus sums (ZG_STRAUS_B = 1, 2 or 4 at zg_create; otherwise by size), bseg_k =
+ *        proofs per segment lane of the b pairs (ZG_BSEG_K at zg_create, at most 32; <= 0 by size),
+ *        halves = waves per proof of the per-proof Miller loop a failing chunk runs (2 below 32,768
+ *        proofs), p7_side = 1 when the b pairs' G1 operands are formed on the side stream. Any out
+ *        pointer may be NULL.
  *   zg_bn254_pairing (tests): e(P, Q) to the power 2u(6u^2 + 3u + 1) (the device's final
  *        exponentiation, see zg_bn254.h): P n x 64 (x, y), Q n x 128 (x.c0, x.c1, y.c0, y.c1),
  *        canonical little-endian Fq; GT n x 384 (12 Fq, coefficients of w^0..w^5 as c0, c1). */
@@ -399,6 +409,7 @@ int zg_pghr13_vk_load_builtin(zg_ctx* ctx);
 int zg_pghr13_vk_load_json(zg_ctx* ctx, const char* json, size_t len);
 int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* inputs, const uint8_t* n_inputs,
                      uint8_t* status, float* kernel_ms);
+int zg_pghr13_shape(zg_ctx* ctx, size_t n, int* straus_b, int* bseg_k, size_t* chunk, int* halves, int* p7_side);
 int zg_bn254_pairing(zg_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt);
 
 /* ---- synthetic workload (bench/tests): Groth16 re-randomization of real proofs,

@@ -160,6 +160,8 @@ extern "C" {
     pub fn zg_pghr13_vk_load_json(ctx: *mut ZgCtx, json: *const c_char, len: usize) -> c_int;
     pub fn zg_pghr13_verify(ctx: *mut ZgCtx, n: usize, proofs: *const u8, inputs: *const u8, n_inputs: *const u8,
                             status: *mut u8, kernel_ms: *mut f32) -> c_int;
+    pub fn zg_pghr13_shape(ctx: *mut ZgCtx, n: usize, straus_b: *mut c_int, bseg_k: *mut c_int, chunk: *mut usize,
+                           halves: *mut c_int, p7_side: *mut c_int) -> c_int;
     pub fn zg_bn254_pairing(ctx: *mut ZgCtx, n: usize, g1: *const u8, g2: *const u8, gt: *mut u8) -> c_int;
 
     pub fn zg_merkle_combine(ctx: *mut ZgCtx, kind: c_int, n: usize, left: *const u8, right: *const u8,

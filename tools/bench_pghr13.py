@@ -45,7 +45,9 @@ def run(ctx, n=65536, reps=3):
     assert st == [0] * n
     km = sum(kms) / len(kms)
     return {"proofs": n, "ms_per_batch": dt * 1e3, "kernel_ms": km, "proofs_per_s": n / dt,
-            "kernel_proofs_per_s": n / (km * 1e-3), "all_ok": True}
+            "kernel_proofs_per_s": n / (km * 1e-3), "all_ok": True,
+            # what the call launched (ZG_STRAUS_B / ZG_BSEG_K / ZG_PGHR_CHUNK as the context read them)
+            "shape": ctx.pghr13_shape(n)}
 
 
 def cpu_baseline(seconds=6.0, threads=1):

@@ -47,6 +47,7 @@ using namespace zg;
                                  // levels (run_pipeline: batches in flight always use K4)
 #define ZG_LINES_LANE_MIN 32768  // straight-line R-chain from here (r03: 64k 14.93 -> 14.47 ms per batch in
                                  // flight; 16k 4.90 -> 5.14 and 8k 3.21 -> 3.63 favour the staged program)
+#define ZG_PGHR_CHUNK 65536      // proofs per batch check of zg_pghr13_verify (ZG_PGHR_CHUNK lowers it, 64 at the least)
 #define ZG_DEFAULT_PAIRS 8       // stream pairs per device (ZG_STREAM_PAIRS overrides, 1..16)
 #define ZG_HI_PAIRS 4            // high-priority stream pairs per device (zg_set_priority round-robin)
 
@@ -69,9 +70,11 @@ BnDev* bn_dev_new();
 void bn_dev_free(BnDev* d);
 int bn_load_vk_json(BnDev* d, hipStream_t st, const char* json, size_t len, const BnKey** out, std::string* err);
 void bn_key_release(BnDev* d, const BnKey* k);
-int bn_pghr13_verify(const BnKey* k, hipStream_t st, hipStream_t side, size_t n, const uint8_t* proofs,
-                     const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho, uint8_t* status,
-                     float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap, std::string* err);
+void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* halves, int* p7_side);
+int bn_pghr13_verify(const BnKey* k, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
+                     const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
+                     uint8_t* status, float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap,
+                     std::string* err);
 int bn_pairing(hipStream_t st, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, std::string* err);
 }  // namespace zg
 
@@ -217,6 +220,10 @@ struct zg_ctx {
   size_t tree_arena_cap = 0;
   void* bn_arena = nullptr;  // zg_pghr13_verify scratch (grow-only, zg_pghr13.hip)
   size_t bn_arena_cap = 0;
+  // the launch shape of zg_pghr13_verify's batch check (zg_pghr13.hip bn_pghr13_shape; zg_pghr13_shape reports it)
+  int pghr_straus_b = 0;     // ZG_STRAUS_B: proofs per lane of k_pghr_straus, 1 / 2 / 4; 0 (any other value) by size
+  int pghr_bseg_k = 0;       // ZG_BSEG_K: proofs per lane of k_pghr_bseg, 1..32 (larger: 32); 0 (or less) by size
+  size_t pghr_chunk = ZG_PGHR_CHUNK;  // ZG_PGHR_CHUNK: proofs per batch check of one call, 64..65,536
   hipEvent_t sig_ev[2] = {};  // around the kernel of the last signature call (zg_last_sig_kernel_ms), first use
   float sig_ms = 0.0f;
 };
@@ -357,6 +364,13 @@ extern "C" zg_ctx* zg_create(const zg_config* cfg) {
   if (const char* e = getenv("ZG_LINES_LANE")) ctx->lines_lane = atoi(e);
   if (const char* e = getenv("ZG_TREE_COOP_BELOW")) ctx->coop_below = (size_t)atol(e);
   if (const char* e = getenv("ZG_DEBUG_EACH")) ctx->debug_each = atoi(e);
+  if (const char* e = getenv("ZG_STRAUS_B")) {
+    const int v = atoi(e);
+    ctx->pghr_straus_b = v == 1 || v == 2 || v == 4 ? v : 0;
+  }
+  if (const char* e = getenv("ZG_BSEG_K")) ctx->pghr_bseg_k = std::max(0, std::min(32, atoi(e)));
+  if (const char* e = getenv("ZG_PGHR_CHUNK"))
+    ctx->pghr_chunk = (size_t)std::max(64L, std::min((long)ZG_PGHR_CHUNK, atol(e)));
   hipError_t e = hipSetDevice(ctx->device);
   auto A = [&](hipError_t r) {
     if (e == hipSuccess) e = r;
@@ -2152,7 +2166,6 @@ extern "C" int zg_pghr13_vk_load_builtin(zg_ctx* ctx) {
   return zg_pghr13_vk_load_json(ctx, ZG_PGHR13_VK_JSON, strlen(ZG_PGHR13_VK_JSON));
 }
 
-#define ZG_PGHR_CHUNK ((size_t)65536)
 extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* inputs,
                                 const uint8_t* n_inputs, uint8_t* status, float* kernel_ms) {
   if (!ctx || (n && (!proofs || !inputs || !status)) || n > (1u << 24)) return ZG_E_INVAL;
@@ -2191,18 +2204,19 @@ extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, co
   } else if (!os_random(rho.data(), rho.size())) {
     return fail(ctx, ZG_E_INVAL, "getrandom failed");
   }
-  // one batch check per chunk of at most ZG_PGHR_CHUNK proofs: the call's arena (~27 KB per proof,
+  // one batch check per chunk of at most ctx->pghr_chunk proofs: the call's arena (~27 KB per proof,
   // mostly the b lines) stays bounded at the chunk size however large the caller's window is
   if (kernel_ms) *kernel_ms = 0;
   bool any_failed = false;
-  for (size_t o = 0; o < n; o += ZG_PGHR_CHUNK) {
-    const size_t m = n - o < ZG_PGHR_CHUNK ? n - o : ZG_PGHR_CHUNK;
+  const size_t chunk = ctx->pghr_chunk;
+  for (size_t o = 0; o < n; o += chunk) {
+    const size_t m = n - o < chunk ? n - o : chunk;
     bool batch_failed = false;
     float ms = 0;
-    const int rc = bn_pghr13_verify(ctx->bn_key, ctx->stream, ctx->side, m, proofs + 296 * o, inputs + 9 * 32 * o,
-                                    n_inputs ? n_inputs + o : nullptr, rho.data() + 80 * o, status + o,
-                                    kernel_ms ? &ms : nullptr, &batch_failed, &ctx->bn_arena, &ctx->bn_arena_cap,
-                                    &ctx->err);
+    const int rc = bn_pghr13_verify(ctx->bn_key, ctx->stream, ctx->side, m, ctx->pghr_straus_b, ctx->pghr_bseg_k,
+                                    proofs + 296 * o, inputs + 9 * 32 * o, n_inputs ? n_inputs + o : nullptr,
+                                    rho.data() + 80 * o, status + o, kernel_ms ? &ms : nullptr, &batch_failed,
+                                    &ctx->bn_arena, &ctx->bn_arena_cap, &ctx->err);
     if (rc != ZG_OK) return rc;
     if (kernel_ms) *kernel_ms += ms;
     any_failed = any_failed || batch_failed;
@@ -2211,6 +2225,20 @@ extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, co
     ctx->stats[8]++;
     if (any_failed) ctx->stats[9]++;
   }
+  return ZG_OK;
+}
+
+extern "C" int zg_pghr13_shape(zg_ctx* ctx, size_t n, int* straus_b, int* bseg_k, size_t* chunk, int* halves,
+                               int* p7_side) {
+  if (!ctx) return ZG_E_INVAL;
+  const size_t first = n < ctx->pghr_chunk ? n : ctx->pghr_chunk;
+  int B, K, hv, p7;
+  bn_pghr13_shape(first, ctx->pghr_straus_b, ctx->pghr_bseg_k, &B, &K, &hv, &p7);
+  if (straus_b) *straus_b = B;
+  if (bseg_k) *bseg_k = K;
+  if (chunk) *chunk = ctx->pghr_chunk;
+  if (halves) *halves = hv;
+  if (p7_side) *p7_side = p7;
   return ZG_OK;
 }
 

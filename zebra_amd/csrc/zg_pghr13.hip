@@ -420,9 +420,8 @@ __global__ void __launch_bounds__(64) k_pghr_p7(int n, const PghrDec* dec, const
   pts[i].qb = d.qb;
 }
 // B by size: enough (family, group) lanes for ~2 waves per SIMD, the rest as shared doublings (B = 4
-// keeps its 4 x 3 points in scratch)
-static int straus_b(size_t n) {
-  static const int forced = getenv("ZG_STRAUS_B") ? atoi(getenv("ZG_STRAUS_B")) : 0;
+// keeps its 4 x 3 points in scratch); forced: the context's ZG_STRAUS_B (1, 2 or 4; anything else: by size)
+static int straus_b(size_t n, int forced) {
   if (forced == 1 || forced == 2 || forced == 4) return forced;
   return n >= 28672 ? 2 : 1;  // 64k: B = 1 / 2 / 4 28.6 / 28.1 / 30.0 ms (profiles/r03s5_pghr13_bench.txt)
 }
@@ -925,11 +924,10 @@ void bn_dev_free(BnDev* d) {
   } while (0)
 
 static unsigned bn_blocks(long long n) { return (unsigned)((n + 63) / 64); }
-// k_pghr_bseg's proofs per lane (ZG_BSEG_K overrides): ceil(n / K) >= 8,192 lanes x 8 segments
-// (1,024 waves of the one-wave-per-SIMD kernel), the rest as shared squarings: 64k proofs K = 8
-// (kernels 39.0 / 36.0 / 34.6 / 32.9 ms for K = 1 / 2 / 4 / 8, profiles/r03v_pghr13_bench.txt)
-static int bseg_k(size_t n) {
-  static const int forced = getenv("ZG_BSEG_K") ? atoi(getenv("ZG_BSEG_K")) : 0;
+// k_pghr_bseg's proofs per lane (forced: the context's ZG_BSEG_K; <= 0: by size): ceil(n / K) >= 8,192
+// lanes x 8 segments (1,024 waves of the one-wave-per-SIMD kernel), the rest as shared squarings: 64k
+// proofs K = 8 (kernels 39.0 / 36.0 / 34.6 / 32.9 ms for K = 1 / 2 / 4 / 8, profiles/r03v_pghr13_bench.txt)
+static int bseg_k(size_t n, int forced) {
   if (forced > 0) return forced < 32 ? forced : 32;
   int k = 1;
   while (k < 8 && n / (size_t)(2 * k) >= 8192) k *= 2;
@@ -1066,11 +1064,24 @@ int bn_load_vk_json(BnDev* d, hipStream_t st, const char* json, size_t len, cons
   return ZG_OK;
 }
 
-int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n, const uint8_t* proofs,
-                     const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho, uint8_t* status,
-                     float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap, std::string* err) {
+// the launch shape of one chunk of n proofs (zg_pghr13_shape reports it, bn_pghr13_verify launches by
+// it): proofs per Straus lane, proofs per segment lane, the per-proof Miller loop's waves per proof
+// (a failing chunk only), P_i7 on the side stream
+void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* halves, int* p7_side) {
+  *B = straus_b(n, forced_b);
+  *K = bseg_k(n, forced_k);
+  *halves = n < ZG_PGHR_SPLIT_BELOW ? 2 : 1;
+  *p7_side = n >= 32768;
+}
+
+int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
+                     const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
+                     uint8_t* status, float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap,
+                     std::string* err) {
   if (batch_failed) *batch_failed = false;
   if (!n) return ZG_OK;
+  int B, K, halves, p7_on_side;
+  bn_pghr13_shape(n, forced_b, forced_k, &B, &K, &halves, &p7_on_side);
   // the call's device buffers, carved from the context's grow-only arena (a 64k call needs
   // ~1.5 GB; allocating and freeing that per call cost more wall time than most kernels)
   const unsigned nb = bn_blocks(n);
@@ -1170,7 +1181,7 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   // the b pairs' operands P_i7 (one GLV product + combs per proof): on the side stream after the b
   // lines from 32k proofs, where the main stream's Straus sums are the longer chain; below, the side
   // stream's G2 chain (128 waves of decodes and lines at 8k) is, and P_i7 follows the sums on main
-  const bool p7_side = n >= 32768;
+  const bool p7_side = p7_on_side != 0;
   if (p7_side) {
     BCHK(hipEventRecord(stready, st));
     BCHK(hipStreamWaitEvent(side, stready, 0));
@@ -1180,7 +1191,6 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   BCHK(hipEventRecord(g2join, side));
   // the six key pairs' operand sums (Straus over the GLV halves, B proofs per lane), concurrent with
   // the side stream's b lines and P_i7
-  const int B = straus_b(n);
   const long long G = ((long long)n + B - 1) / B;
   const dim3 sg((unsigned)((G + 63) / 64), ZG_PGHR_NFAM);
   if (B == 4)
@@ -1203,7 +1213,6 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   // dseg[0..S); the easy part of the S values, their Horner product and ONE hard part
   BCHK(hipMemsetAsync(dbst, ZG_STATUS_OK, ZG_PGHR_FSEG + 1, st));
   BCHK(hipStreamWaitEvent(st, g2join, 0));
-  const int K = bseg_k(n);
   const unsigned gb = 1 + bn_blocks(((long long)n + K - 1) / K);  // + the key pairs' block
   hipLaunchKernelGGL(k_pghr_bseg, dim3(gb, ZG_PGHR_FSEG), dim3(64), 0, st, (int)n, K, dpts, dst, dbl, dagg, d->lines,
                      dbseg);
@@ -1227,7 +1236,6 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
     hipLaunchKernelGGL(k_pghr_rho, dim3(nb), dim3(64 * ZG_PGHR_NMUL), 0, st, (int)n, ddec, drho, dst, dmul);
     hipLaunchKernelGGL(k_pghr_combine, dim3(nb), dim3(64), 0, st, (int)n, ddec, dmul, drho, d->comb, dst, dpts);
     BCHK(hipGetLastError());
-    const int halves = n < ZG_PGHR_SPLIT_BELOW ? 2 : 1;
     hipLaunchKernelGGL(k_pghr_miller, dim3(nb), dim3(64 * halves), 0, st, (int)n, dpts, d->lines, dst, df, halves);
     BCHK(hipGetLastError());
     hipLaunchKernelGGL(k_fe_easy, dim3(nb), dim3(64), 0, st, (int)n, df, dst, dw, halves);

@@ -102,6 +102,8 @@ def lib():
         L.zg_pghr13_vk_load_builtin.argtypes = [vp]
         L.zg_pghr13_vk_load_json.argtypes = [vp, u8p, sz]
         L.zg_pghr13_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(ctypes.c_float)]
+        ip = ctypes.POINTER(ctypes.c_int)
+        L.zg_pghr13_shape.argtypes = [vp, sz, ip, ip, ctypes.POINTER(ctypes.c_size_t), ip, ip]
         L.zg_bn254_pairing.argtypes = [vp, sz, u8p, u8p, u8p]
         L.zg_tree_empty_roots.argtypes = [vp, i, sz, u8p]
         L.zg_tree_state_max_bytes.restype = sz
@@ -539,6 +541,16 @@ class Context:
         self._chk(lib().zg_pghr13_verify(self._p, n, pblob, iblob, cnt, st, ctypes.byref(ms)))
         out = list(st.raw[:n])
         return (out, ms.value) if with_time else out
+
+    def pghr13_shape(self, n):
+        """what pghr13_verify of n proofs would launch on this context (include/zg.h zg_pghr13_shape;
+        nothing runs): {"straus_b", "bseg_k", "chunk", "halves", "p7_side"}, B / K / halves / p7_side
+        of the first chunk. ZG_STRAUS_B, ZG_BSEG_K and ZG_PGHR_CHUNK are read when the context is created."""
+        b, k, h, p7 = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        ch = ctypes.c_size_t(0)
+        self._chk(lib().zg_pghr13_shape(self._p, n, ctypes.byref(b), ctypes.byref(k), ctypes.byref(ch),
+                                        ctypes.byref(h), ctypes.byref(p7)))
+        return {"straus_b": b.value, "bseg_k": k.value, "chunk": ch.value, "halves": h.value, "p7_side": p7.value}
 
     def bn254_pairing(self, g1s, g2s):
         """device pairing (tests): g1 (x, y) ints, g2 ((x0, x1), (y0, y1)) -> 12 ints per GT"""
