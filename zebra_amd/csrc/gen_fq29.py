@@ -328,6 +328,13 @@ def main():
     body += redc_full([("r", "acc", lambda k: sq_terms("a", "A2", k))])
     o += fn("fq29d_sqr", "uint32_t* r, const uint32_t* a", body,
             ["r = a^2 2^-406 mod p in digits (a < 2p) -> r < 2p; r may not alias a."])
+    body = redc_full([("r", "acc", lambda k: terms("a", "b", k) + terms("c", "d", k))])
+    o += fn("fq29d_dot2", "uint32_t* r, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d",
+            body,
+            ["r = (a b + c d) 2^-406 mod p in digits: a sum of two products under one reduction (the c0 chain of",
+             "f2d_mul29 alone; a point formula's Y3 = rr W - Y1 (2J) as rr W + (k p - Y1)(2J)). All four operands",
+             "normalized (digits < 2^29): 14 (2^58 + 2^58) + 14 2^58 < 2^64 per column. Output normalized,",
+             "< (a b + c d) / 2^406 + p. r may alias no operand."])
     body = ["  uint32_t A[14];"] + split("A", "a")
     body += redc_full([("r", "acc", lambda k: terms("A", "FQ29D_KIN", k))])
     o += fn("fq29d_from_mont", "uint32_t* r, const uint32_t* a",

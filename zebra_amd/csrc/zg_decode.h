@@ -107,6 +107,25 @@ __global__ void __launch_bounds__(64, ZG_DECODE_WPE) k_decode_glv_lds(BatchBufs 
 }
 #endif
 
+#if ZG_DECODE_FQD && ZG_SUBGROUP_XX
+// the point a subgroup check adds again and again (g1_in_subgroup_xx: X, Y, Z, Z^2, Z^3) in LDS,
+// [value][digit][lane]: the bank depends on the lane alone, each lane reads what it wrote (no barrier).
+// 5 x 14 x 64 words = 17.5 KB per one-wave block, 140 KB for the 8 blocks of a CU at two waves per SIMD.
+struct G1HoldLds {
+  uint32_t* base;  // the block's array + lane
+  __device__ __forceinline__ void put(int k, const FqD& v) const {
+#pragma unroll
+    for (int d = 0; d < 14; d++) base[(k * 14 + d) * 64] = v.d[d];
+  }
+  __device__ __forceinline__ FqD get(int k) const {
+    FqD v;
+#pragma unroll
+    for (int d = 0; d < 14; d++) v.d[d] = base[(k * 14 + d) * 64];
+    return v;
+  }
+};
+#endif
+
 // JOB < 0: every job in one launch (grid 4G, the product's only launch; JOB = -2: every job but the
 // GLV products of the K4 layout, grid 3G, after k_decode_glv_lds); JOB = 0 / 1 / 2: that job
 // alone (grid G / 2G / G: round 4's per-job profiles, profiles/r04b_kernel_stats_decode_split.csv,
@@ -138,7 +157,13 @@ __global__ void __launch_bounds__(64, ZG_DECODE_WPE) k_decode_points(BatchBufs b
   const G1A p = b.ptAC[(size_t)role * b.npad + i];
   const bool ok = !p.inf;
   if (job == 1) {
+#if ZG_DECODE_FQD && ZG_SUBGROUP_XX
+    __shared__ uint32_t lds_hold[5 * 14 * 64];
+    const G1HoldLds hold{lds_hold + (threadIdx.x & 63)};
+    b.okbits[3 * i + role] = ok && g1_in_subgroup_xx(p, hold);
+#else
     b.okbits[3 * i + role] = ok && ZG_DEC_SUBGROUP(p);
+#endif
     return;
   }
   uint64_t ra = 0, rb = 0;

@@ -173,6 +173,16 @@ ZG_INL FqD fqd_sub2(const FqD& a, const FqD& b, const FqD& c) {
   fqd_norm(r.d);
   return r;
 }
+// -x for x < 2p: 3p - x < 3p
+ZG_INL FqD fqd_neg2(const FqD& x) { return fqd_sub<3, 0, 1>(fqd_zero(), x); }
+// (a b + c d) / 2^406 mod p under one reduction (fq29d_dot2), all four operands normalized:
+// < 2p for Ka Kb + Kc Kd < 2^25. Four operands do not fit the register arguments of an out-of-line
+// product (two u32x16 fill v0..v31), so it is inlined at its call sites: one per point formula.
+ZG_INL FqD fqd_dot2(const FqD& a, const FqD& b, const FqD& c, const FqD& d) {
+  FqD r;
+  fq29d_dot2(r.d, a.d, b.d, c.d, d.d);
+  return r;
+}
 // v == 0 mod p for a product output or any v < 2p (normalized digits are unique: v is 0 or p)
 ZG_INL bool fqd_is_zero2(const FqD& v) {
   constexpr FqDK p1 = fqd_kp(1, 0);
@@ -377,10 +387,25 @@ ZG_INL Fq2 f2d_to_w(const Fq2D& a) {
 }
 
 // ------------------------------------------------------------------ G1 Jacobian (y^2 = x^3 + 4)
-// Invariant of every G1D below: X < 35p, Y < 19p, Z < 4p; infinity is Z == 0 mod p.
+// ZG_G1D_DOT2 (default 1): every point formula closes its Y3 as one sum of two products under one
+// reduction (fqd_dot2), and the doubling forms D = 4 X B as a product: one reduction fewer per
+// doubling and per addition; 0: dbl-2009-l / madd-2007-bl / add-2007-bl with Y3 as two reduced
+// products and a difference (the A/B reference). The same elements of Fq either way.
+#ifndef ZG_G1D_DOT2
+#define ZG_G1D_DOT2 1
+#endif
+// Invariant of every G1D below: X < G1D_KX p, Y < G1D_KY p, Z < 4p; infinity is Z == 0 mod p.
+// With fqd_dot2 X < 19p (a doubling's X3), Y < 4p (an affine operand's -y; every formula's Y3 < 2p);
+// without it X < 35p, Y < 19p.
+#if ZG_G1D_DOT2
+static constexpr int G1D_KX = 19, G1D_KY = 4;
+#else
+static constexpr int G1D_KX = 35, G1D_KY = 19;
+#endif
 struct G1D {
   FqD x, y, z;
 };
+#define G1D_CHK(p) (FQD_CHK((p).x, G1D_KX), FQD_CHK((p).y, G1D_KY), FQD_CHK((p).z, 4))
 
 ZG_INL bool g1d_is_inf(const G1D& p) { return fqd_is_zero4(p.z); }
 ZG_INL G1D g1d_from_aff(const FqD& x, const FqD& y) { return {x, y, fqd_one()}; }
@@ -388,6 +413,27 @@ ZG_INL G1D g1d_infinity() { return {fqd_one(), fqd_one(), fqd_zero()}; }
 // canonical word-form Jacobian (the same point; Z = 0 stays infinity)
 ZG_INL G1J g1d_to_jac(const G1D& p) { return {fqd_to(p.x), fqd_to(p.y), fqd_to(p.z)}; }
 
+#if ZG_G1D_DOT2
+// dbl-2009-l (a = 0) with D = 2((X + B)^2 - A - C) = 4 X B as one product and
+// Y3 = E (D - X3) - 8C = E W + (3p - B)(8B) under one reduction: C = B^2 and T = (X + B)^2 are
+// never formed. 6 reductions. In: the invariant. Out: X < 19p, Y < 2p, Z < 4p.
+// Infinity (Z = 0) doubles to Z = 2 Y Z = 0.
+ZG_INL G1D g1d_dbl(const G1D& p) {
+  G1D_CHK(p);
+  const FqD A = fqd_sqr(p.x);                              // < 2
+  const FqD B = fqd_sqr(p.y);                              // < 2
+  const FqD D = fqd_smul<4>(fqd_mul(p.x, B));              // 4 (19 x 2 -> < 2): < 8
+  const FqD E = fqd_smul<3>(A);                            // < 6
+  const FqD F = fqd_sqr(E);                                // < 2
+  const FqD X3 = fqd_sub<17, 1, 2>(F, D);                  // F - 2D + 17p: < 19 (2D < 16)
+  const FqD W = fqd_sub<20, 1, 1>(D, X3);                  // D - X3 + 20p: < 28 (X3 < 19)
+  const FqD nB = fqd_neg2(B), B8 = fqd_smul<8>(B);         // 3p - B < 3, 8B < 16 (both normalized)
+  const FqD Y3 = fqd_dot2(E, W, nB, B8);                   // 6 x 28 + 3 x 16 = 216: < 2
+  const FqD Z3 = fqd_smul<2>(fqd_mul(p.y, p.z));           // < 4
+  FQD_CHK(D, 8), FQD_CHK(X3, 19), FQD_CHK(W, 28), FQD_CHK(nB, 3), FQD_CHK(B8, 16), FQD_CHK(Y3, 2), FQD_CHK(Z3, 4);
+  return {X3, Y3, Z3};
+}
+#else
 // dbl-2009-l (a = 0), 7 products. In: the invariant. Out: X < 31p, Y < 19p, Z < 4p.
 // Infinity (Z = 0) doubles to Z = 2 Y Z = 0.
 ZG_INL G1D g1d_dbl(const G1D& p) {
@@ -404,12 +450,15 @@ ZG_INL G1D g1d_dbl(const G1D& p) {
   const FqD Z3 = fqd_smul<2>(fqd_mul(p.y, p.z));           // < 4
   return {X3, Y3, Z3};
 }
+#endif
 
 // g1d_dbl on a whole wave for a lone doubling chain (K4's top-window scaling, zg_msm.hip): the same
-// formulas and bounds, so the same digits, with the seven products of dbl-2009-l in three levels of
-// independent products, one per lane (lanes 0..2), exchanged through `xch` (3 FqD of LDS, the wave's
-// own): {A = X^2, B = Y^2, YZ}, {C = B^2, T = (X + B)^2, F = (3A)^2}, {E (D - X3)}. Every lane of the
-// wave calls it with the same p and gets the result.
+// formulas and bounds, so the same digits, with the products in three levels of independent
+// products, one per lane, exchanged through `xch` (3 FqD of LDS, the wave's own). With fqd_dot2:
+// {A = X^2, B = Y^2, YZ}, {X B, F = (3A)^2}, {Y3 = E W + (3p - B)(8B)}, the last on every lane
+// alike (its operands are wave-uniform: nothing to exchange). Without: {A, B, YZ},
+// {C = B^2, T = (X + B)^2, F}, {E (D - X3)}. Every lane of the wave calls it with the same p and
+// gets the result.
 ZG_INL FqD fqd_pick3(int k, const FqD& a, const FqD& b, const FqD& c) {
   FqD r;
 #pragma unroll
@@ -427,8 +476,19 @@ ZG_INL G1D g1d_dbl_wave(const G1D& p, FqD* xch) {
   fqd_xch_put(xch, lane, m1);
   const FqD A = xch[0], B = xch[1], YZ = xch[2];
   __syncthreads();
-  // level 2: C = B^2, T = (X + B)^2, F = E^2 with E = 3 A
   const FqD E = fqd_smul<3>(A);
+#if ZG_G1D_DOT2
+  // level 2: X B, F = E E (lane 2 repeats F)
+  const FqD m2 = fqd_mul(fqd_pick3(k, p.x, E, E), fqd_pick3(k, B, E, E));
+  fqd_xch_put(xch, lane, m2);
+  const FqD XB = xch[0], F = xch[1];
+  __syncthreads();
+  const FqD D = fqd_smul<4>(XB);
+  const FqD X3 = fqd_sub<17, 1, 2>(F, D);
+  // level 3: one sum of two products, the same on every lane
+  const FqD Y3 = fqd_dot2(E, fqd_sub<20, 1, 1>(D, X3), fqd_neg2(B), fqd_smul<8>(B));
+#else
+  // level 2: C = B^2, T = (X + B)^2, F = E^2 with E = 3 A
   const FqD m2 = fqd_sqr(fqd_pick3(k, B, fqd_add(p.x, B), E));
   fqd_xch_put(xch, lane, m2);
   const FqD C = xch[0], T = xch[1], F = xch[2];
@@ -441,21 +501,44 @@ ZG_INL G1D g1d_dbl_wave(const G1D& p, FqD* xch) {
   const FqD Y3a = xch[0];
   __syncthreads();
   const FqD Y3 = fqd_sub<17, 1, 1>(Y3a, fqd_smul<8>(C));
+#endif
   const FqD Z3 = fqd_smul<2>(YZ);
   return {X3, Y3, Z3};
 }
 
+// The close of both additions: X3 = rr^2 - J - 2V, Y3 = rr (V - X3) - 2 Y J for Y = Y1 (mixed) or
+// S1 (full), Y < KYB p, rr < 43p. With fqd_dot2 Y3 = rr W + ((KYB + 1) p - Y)(2J) under one
+// reduction (< 2p); without, two reduced products and a difference (< 7p, needs Y J < 2p).
+template <int KYB>
+ZG_INL void g1d_add_close(FqD& X3, FqD& Y3, const FqD& rr, const FqD& RR, const FqD& J, const FqD& V, const FqD& Y) {
+  X3 = fqd_sub2<7>(RR, J, fqd_smul<2>(V));                 // rr^2 - J - 2V + 7p: < 9 (J + 2V < 6)
+  const FqD W = fqd_sub<10, 1, 1>(V, X3);                  // V - X3 + 10p: < 12
+#if ZG_G1D_DOT2
+  const FqD nY = fqd_sub<KYB + 1, 0, 1>(fqd_zero(), Y);    // (KYB + 1) p - Y: < KYB + 1 (normalized)
+  const FqD J2 = fqd_smul<2>(J);                           // < 4
+  Y3 = fqd_dot2(rr, W, nY, J2);                            // 43 x 12 + 5 x 4 = 536: < 2
+  FQD_CHK(nY, KYB + 1), FQD_CHK(J2, 4), FQD_CHK(Y3, 2);
+#else
+  Y3 = fqd_sub<5, 1, 2>(fqd_mul(rr, W), fqd_mul(Y, J));    // rr W - 2 Y J + 5p: < 7 (2 Y J < 4)
+  FQD_CHK(Y3, 7);
+#endif
+  FQD_CHK(X3, 9), FQD_CHK(W, 12);
+}
+
 // madd-2007-bl with complete case handling: p + q for q affine and finite, qx < 2p, qy < 4p.
-// In: the invariant. Out: X < 9p, Y < 7p, Z < 4p (or g1d_dbl's, or q itself). 11 products.
+// In: the invariant. Out: X < 9p, Y < 2p (7p without fqd_dot2), Z < 4p (or g1d_dbl's, or q itself).
+// 10 reductions (11 without fqd_dot2).
 ZG_INL G1D g1d_add_aff(const G1D& p, const FqD& qx, const FqD& qy) {
+  G1D_CHK(p), FQD_CHK(qx, 2), FQD_CHK(qy, 4);
   if (g1d_is_inf(p)) return g1d_from_aff(qx, qy);
   const FqD Z1Z1 = fqd_sqr(p.z);                           // < 2
   const FqD U2 = fqd_mul(qx, Z1Z1);                        // < 2
   const FqD S2 = fqd_mul(fqd_mul(qy, p.z), Z1Z1);          // < 2
-  const FqD H = fqd_sub<36, 1, 1>(U2, p.x);                // U2 - X1 + 36p: < 38 (X1 < 35)
-  const FqD rr = fqd_sub<39, 2, 2>(S2, p.y);               // 2 S2 - 2 Y1 + 39p: < 43 (2 Y1 < 38)
+  const FqD H = fqd_sub<G1D_KX + 1, 1, 1>(U2, p.x);        // U2 - X1 + (KX + 1) p: < KX + 3 (22; 38)
+  const FqD rr = fqd_sub<2 * G1D_KY + 1, 2, 2>(S2, p.y);   // 2 S2 - 2 Y1 + (2 KY + 1) p: < 2 KY + 5 (13; 43)
   const FqD HH = fqd_sqr(H);                               // < 2
   const FqD RR = fqd_sqr(rr);                              // < 2
+  FQD_CHK(H, G1D_KX + 3), FQD_CHK(rr, 2 * G1D_KY + 5);
   // H == 0 mod p <=> H^2 == 0 (and rr likewise): P == +-Q
   if (fqd_is_zero2(HH)) {
     if (fqd_is_zero2(RR)) return g1d_dbl(p);
@@ -464,28 +547,33 @@ ZG_INL G1D g1d_add_aff(const G1D& p, const FqD& qx, const FqD& qy) {
   const FqD I = fqd_smul<4>(HH);                           // < 8
   const FqD J = fqd_mul(H, I);                             // < 2
   const FqD V = fqd_mul(p.x, I);                           // < 2
-  const FqD X3 = fqd_sub2<7>(RR, J, fqd_smul<2>(V));       // rr^2 - J - 2V + 7p: < 9 (J + 2V < 6)
-  const FqD Y3a = fqd_mul(rr, fqd_sub<10, 1, 1>(V, X3));   // (V - X3 + 10p < 12) rr: < 2
-  const FqD Y3 = fqd_sub<5, 1, 2>(Y3a, fqd_mul(p.y, J));   // - 2 Y1 J + 5p: < 7 (2 Y1 J < 4)
-  const FqD Z3 = fqd_smul<2>(fqd_mul(p.z, H));             // (Z1 + H)^2 - Z1Z1 - HH = 2 Z1 H: < 4
-  return {X3, Y3, Z3};
+  G1D r;
+  g1d_add_close<G1D_KY>(r.x, r.y, rr, RR, J, V, p.y);      // Y1 < KY (Y1 J < 2)
+  r.z = fqd_smul<2>(fqd_mul(p.z, H));                      // (Z1 + H)^2 - Z1Z1 - HH = 2 Z1 H: < 4
+  return r;
 }
 
-// add-2007-bl with complete case handling: p + q, both in the invariant (either may be infinity).
-// Out: X < 9p, Y < 7p, Z < 4p (or g1d_dbl's, or p / q itself). 16 products.
-ZG_INL G1D g1d_add_full(const G1D& p, const G1D& q) {
-  if (g1d_is_inf(p)) return q;
-  if (g1d_is_inf(q)) return p;
+// add-2007-bl with complete case handling and q's Z2Z2 = Z2^2, Z2C = Z2^3 given (both < 2p; a chain
+// that adds one Jacobian point again and again forms them once): p + q, both in the invariant
+// (either may be infinity). q is read from a store Hold where it is used -- get(k): 0 X2, 1 Y2,
+// 2 Z2, 3 Z2^2, 4 Z2^3 -- so a chain may hold it outside its registers (G1HoldLds, zg_decode.h).
+// Out: X < 9p, Y < 2p (7p without fqd_dot2), Z < 4p (or g1d_dbl's, or p / q itself).
+// 13 reductions (14 without fqd_dot2).
+template <class Hold>
+ZG_INL G1D g1d_readd_t(const G1D& p, const Hold& h) {
+  G1D_CHK(p);
+  if (g1d_is_inf(p)) return {h.get(0), h.get(1), h.get(2)};
+  if (fqd_is_zero4(h.get(2))) return p;
   const FqD Z1Z1 = fqd_sqr(p.z);                           // (Z1 < 4)^2: < 2
-  const FqD Z2Z2 = fqd_sqr(q.z);                           // < 2
-  const FqD U1 = fqd_mul(p.x, Z2Z2);                       // 35 x 2: < 2
-  const FqD U2 = fqd_mul(q.x, Z1Z1);                       // < 2
-  const FqD S1 = fqd_mul(fqd_mul(p.y, q.z), Z2Z2);         // (19 x 4 -> < 2) x 2: < 2
-  const FqD S2 = fqd_mul(fqd_mul(q.y, p.z), Z1Z1);         // < 2
+  const FqD U1 = fqd_mul(p.x, h.get(3));                   // KX x 2: < 2
+  const FqD U2 = fqd_mul(h.get(0), Z1Z1);                  // < 2
+  const FqD S1 = fqd_mul(p.y, h.get(4));                   // KY x 2: < 2
+  const FqD S2 = fqd_mul(fqd_mul(h.get(1), p.z), Z1Z1);    // (KY x 4 -> < 2) x 2: < 2
   const FqD H = fqd_sub<3, 1, 1>(U2, U1);                  // U2 - U1 + 3p: < 5 (U1 < 2)
   const FqD rr = fqd_sub<5, 2, 2>(S2, S1);                 // 2 S2 - 2 S1 + 5p: < 9 (2 S1 < 4)
   const FqD HH = fqd_sqr(H);                               // < 2
   const FqD RR = fqd_sqr(rr);                              // < 2
+  FQD_CHK(H, 5), FQD_CHK(rr, 9);
   // H == 0 mod p <=> H^2 == 0 (and rr likewise): P == +-Q
   if (fqd_is_zero2(HH)) {
     if (fqd_is_zero2(RR)) return g1d_dbl(p);
@@ -494,19 +582,74 @@ ZG_INL G1D g1d_add_full(const G1D& p, const G1D& q) {
   const FqD I = fqd_smul<4>(HH);                           // (2H)^2: < 8
   const FqD J = fqd_mul(H, I);                             // 5 x 8: < 2
   const FqD V = fqd_mul(U1, I);                            // < 2
-  const FqD X3 = fqd_sub2<7>(RR, J, fqd_smul<2>(V));       // rr^2 - J - 2V + 7p: < 9 (J + 2V < 6)
-  const FqD Y3a = fqd_mul(rr, fqd_sub<10, 1, 1>(V, X3));   // (V - X3 + 10p < 12) x (rr < 9): < 2
-  const FqD Y3 = fqd_sub<5, 1, 2>(Y3a, fqd_mul(S1, J));    // - 2 S1 J + 5p: < 7 (2 S1 J < 4)
-  const FqD Z3 = fqd_smul<2>(fqd_mul(fqd_mul(p.z, q.z), H));  // 2 Z1 Z2 H: (16 -> < 2) x 5 -> < 2, x 2: < 4
-  return {X3, Y3, Z3};
+  G1D r;
+  g1d_add_close<2>(r.x, r.y, rr, RR, J, V, S1);            // S1 < 2 (S1 J < 2)
+  r.z = fqd_smul<2>(fqd_mul(fqd_mul(p.z, h.get(2)), H));   // 2 Z1 Z2 H: (16 -> < 2) x 5 -> < 2, x 2: < 4
+  return r;
+}
+// the plain store: five FqD of the caller's own (registers, or the private segment)
+struct G1Hold {
+  FqD v[5];
+  ZG_HD void put(int k, const FqD& x) { v[k] = x; }
+  ZG_HD FqD get(int k) const { return v[k]; }
+};
+ZG_INL G1D g1d_readd(const G1D& p, const G1D& q, const FqD& Z2Z2, const FqD& Z2C) {
+  G1D_CHK(q), FQD_CHK(Z2Z2, 2), FQD_CHK(Z2C, 2);
+  return g1d_readd_t(p, G1Hold{{q.x, q.y, q.z, Z2Z2, Z2C}});
 }
 
-// -x for x < 2p: 3p - x < 3p
-ZG_INL FqD fqd_neg2(const FqD& x) { return fqd_sub<3, 0, 1>(fqd_zero(), x); }
+// add-2007-bl with complete case handling: p + q, both in the invariant (either may be infinity):
+// g1d_readd after Z2^2 and Z2^3. 15 reductions (16 without fqd_dot2).
+ZG_INL G1D g1d_add_full(const G1D& p, const G1D& q) {
+  if (g1d_is_inf(p)) return q;
+  if (g1d_is_inf(q)) return p;
+  const FqD Z2Z2 = fqd_sqr(q.z);                           // < 2
+  return g1d_readd(p, q, Z2Z2, fqd_mul(q.z, Z2Z2));        // 4 x 2: < 2
+}
 
-// G1 subgroup check (zg_curve.h g1_in_subgroup, same test): sigma(P) == -[x^2] P with the
-// 127 doublings and 16 mixed additions in FqD
+// G1 subgroup check (zg_curve.h g1_in_subgroup, same test): sigma(P) == -[x^2] P in FqD.
+// ZG_SUBGROUP_XX (default 0: built, measured, off -- DESIGN.md 4f): [x^2] P = [|x|]([|x|] P), two
+// walks of |x| = 0xd201000000010000 (weight 6): 63 doublings and 5 additions each, 126 + 10 point
+// operations against the 127 + 16 of one walk of the 128-bit x^2 (weight 17). Both walks run the
+// same loop body, g1d_dbl and g1d_readd_t of a held Jacobian point T with T.z^2 and T.z^3 beside
+// it: T = (P.x, P.y, 1) first (three products by 1 per addition more than a mixed addition, 15 in
+// all, for one copy of the code), then T = Q = [|x|] P. T lives in the store `hold` (five FqD: held
+// in registers beside the walk's state they cost the decode kernel 588 spilled VGPRs; the kernel
+// keeps them in LDS, G1HoldLds of zg_decode.h). Every case is handled by g1d_readd_t: for a point
+// outside G1 Q or any intermediate may be the point at infinity or +-T. 0: the one walk of x^2
+// with mixed additions of P.
+#ifndef ZG_SUBGROUP_XX
+#define ZG_SUBGROUP_XX 0
+#endif
+template <class Hold>
+ZG_INL bool g1_in_subgroup_xx(const G1A& p, Hold& hold) {
+  if (p.inf) return true;
+  G1D q = g1d_from_aff(fqd_from(p.x), fqd_from(p.y));
+  hold.put(0, q.x);
+  hold.put(1, q.y);
+  for (int k = 2; k < 5; k++) hold.put(k, fqd_one());
+  for (int pass = 0; pass < 2; pass++) {
+    for (int i = 62; i >= 0; i--) {  // bit 63 of |x| is the leading one
+      q = g1d_dbl(q);
+      if ((BLS_X >> i) & 1ull) q = g1d_readd_t(q, hold);
+    }
+    if (pass == 0) {
+      const FqD zz = fqd_sqr(q.z);
+      hold.put(0, q.x);
+      hold.put(1, q.y);
+      hold.put(2, q.z);
+      hold.put(3, zz);
+      hold.put(4, fqd_mul(q.z, zz));
+    }
+  }
+  const G1A s = {fq_mul(p.x, fq_const(G1_BETA)), fq_neg(p.y), false};
+  return jac_eq_aff(g1d_to_jac(q), s);
+}
 ZG_DEC_INL inline bool g1_in_subgroup_d(const G1A& p) {
+#if ZG_SUBGROUP_XX
+  G1Hold hold;
+  return g1_in_subgroup_xx(p, hold);
+#else
   if (p.inf) return true;
   const FqD px = fqd_from(p.x), py = fqd_from(p.y);
   G1D q = g1d_from_aff(px, py);
@@ -516,6 +659,7 @@ ZG_DEC_INL inline bool g1_in_subgroup_d(const G1A& p) {
   }
   const G1A s = {fq_mul(p.x, fq_const(G1_BETA)), fq_neg(p.y), false};
   return jac_eq_aff(g1d_to_jac(q), s);
+#endif
 }
 
 }  // namespace zg
