@@ -226,7 +226,11 @@ int zg_prep_batch(zg_ctx* ctx, size_t n, const uint8_t* kinds, const uint8_t* fi
  *   zg_redjubjub_verify <- redjubjub::PublicKey::read + verify (sapling-crypto @21084bde), called at
  *        verification/src/sapling.rs:124-137 (spend_auth_sig: vk = rk, msg = rk || sighash,
  *        ZG_GEN_SPEND_AUTH) and :228-238 (binding_sig: vk = bvk, msg = bvk || sighash,
- *        ZG_GEN_BINDING). vk n x 32, sig n x 64 (Rbar || Sbar), msg n x 64, gen n -> ok n (1 / 0)
+ *        ZG_GEN_BINDING). vk n x 32, sig n x 64 (Rbar || Sbar), msg n x 64, gen n -> ok n (1 / 0).
+ *        gen[i] is a two-way selector, not an enumeration that is checked: ZG_GEN_BINDING selects the
+ *        binding generator and EVERY other byte value selects ZG_GEN_SPEND_AUTH's (the reference's
+ *        call sites pass a constant, so there is no error class to mirror); a caller that wants an
+ *        unknown generator refused checks the byte itself.
  *   zg_sapling_bvk      <- the binding verification key of each transaction (sapling.rs:82-94,
  *        216-226, 247-269): sum cv(spends) - sum cv(outputs) - [valueBalance] G_v. cvs: per tx its
  *        n_spends spend cvs then n_outputs output cvs (32 B each), transactions back to back;
