@@ -261,8 +261,8 @@ int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* stat
  *          ZG_ED_SIGNATURE           compress([S]B + [k](-A)) != the 32 bytes of R, k = SHA-512(R ||
  *                                    pubkey || msg) mod l; cofactorless; a non-canonical R never verifies
  *   zg_last_sig_kernel_ms: device time (HIP events on the context stream) of the kernel(s) of the most
- *        recent zg_ed25519_verify, zg_ecdsa_verify, zg_redjubjub_verify, zg_equihash_verify or
- *        zg_headers_verify on this context (measurement helper) */
+ *        recent zg_ed25519_verify, zg_ecdsa_verify, zg_redjubjub_verify, zg_equihash_verify,
+ *        zg_headers_verify or zg_sighash on this context (measurement helper) */
 #define ZG_ED_OK 0
 #define ZG_ED_PUBLIC_ENCODING 1    /* Error::InvalidPublicEncoding */
 #define ZG_ED_SIGNATURE_ENCODING 2 /* Error::InvalidSignatureEncoding */
@@ -299,6 +299,54 @@ int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms);
 #define ZG_ECDSA_PUBKEY_STRIDE 65
 int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* pubkey_len, const uint8_t* sigs,
                     const uint32_t* sig_off, const uint8_t* msg, uint8_t* status);
+
+/* ---- transaction signature hashes on the GPU: the messages the three signature
+ * entries above take, computed from the serialized transactions. Device memory per call, n = 0 and
+ * ntx = 0 as zg_ed25519_verify.
+ *   zg_tx_layout <- Transaction::deserialize chain/src/transaction.rs:249-330, deserialize_join_split
+ *        chain/src/join_split.rs:149-186 and CompactInteger::deserialize
+ *        serialization/src/compact_integer.rs:95-105 over the exact slice tx[0..len). CPU, no context: the
+ *        parser zg_sighash runs per transaction. -> ZG_TX_* (ZG_E_INVAL for a null pointer or len > 2^31);
+ *        out (0 when MALFORMED): [0] header word, [1] inputs, [2] outputs, [3] JoinSplits, [4] Sapling
+ *        spends, [5] Sapling outputs, [6] signature version (0 Sprout, 1 Overwinter, 2 Sapling:
+ *        script/src/sign.rs:331-341), [7] bytes consumed.
+ *          ZG_TX_MALFORMED     deserialize fails: truncated anywhere, an overwintered header that is
+ *                              neither (3, 0x03C48270) nor (4, 0x892F2085), or bytes left over; a count
+ *                              whose elements cannot fit what is left is this, before anything is reserved
+ *          ZG_TX_NONCANONICAL  parses, but a compact size is not the shortest form. The reference reads it
+ *                              and re-encodes it when hashing, so slices of such a transaction are not what
+ *                              it hashes; zcashd rejects the encoding, the chain has none. Reported, not
+ *                              hashed: the caller hashes it on the host.
+ *   zg_sighash <- TransactionInputSigner::signature_hash script/src/sign.rs:152-329 (signature_hash_sprout
+ *        :179-246, signature_hash_post_overwinter :249-329, compute_hash_* :344-474), bit for bit.
+ *        txs: the transactions back to back, transaction t the bytes [tx_off[t], tx_off[t+1]) (ntx + 1
+ *        offsets, not decreasing, at most 2^31 bytes in all); tx_branch_id ntx (read for overwintered
+ *        transactions). Item i: transaction item_tx[i] (< ntx), input_index[i] (ZG_SIGHASH_NO_INPUT: the
+ *        reference's None), script code scripts[script_off[i] .. script_off[i+1]) (n + 1 offsets, not
+ *        decreasing), amount[i] (ignored by the Sprout branch), hashtype[i] (all 32 bits are hashed; base =
+ *        None for 2, Single for 3, else All of hashtype & 0x1f; anyone-can-pay = hashtype & 0x80).
+ *        -> tx_status ntx (ZG_TX_*), hashes n x 32 (H256 storage order: the msg of the signature entries;
+ *        zero for every status but OK), status n:
+ *          ZG_SIGHASH_TX_MALFORMED / _TX_NONCANONICAL  the item's transaction is
+ *          ZG_SIGHASH_INPUT_RANGE  overwintered transaction, input_index >= inputs (the reference indexes
+ *                                  out of bounds and panics)
+ *        A Sprout item whose index is None or >= inputs is OK: the zero hash for Single or anyone-can-pay,
+ *        else the hash with no input matching (sign.rs:180-183; the JoinSplit signature of a v2 transaction).
+ *        ZG_E_INVAL: a null pointer, a decreasing offset table, item_tx[i] >= ntx, more than 2^31 bytes of
+ *        transactions. zg_last_sig_kernel_ms covers the two kernels of this entry. */
+#define ZG_TX_OK 0
+#define ZG_TX_MALFORMED 1
+#define ZG_TX_NONCANONICAL 2
+#define ZG_SIGHASH_OK 0
+#define ZG_SIGHASH_TX_MALFORMED 1
+#define ZG_SIGHASH_TX_NONCANONICAL 2
+#define ZG_SIGHASH_INPUT_RANGE 3
+#define ZG_SIGHASH_NO_INPUT 0xFFFFFFFFu
+int zg_tx_layout(const uint8_t* tx, size_t len, uint64_t* out);
+int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
+               size_t n, const uint32_t* item_tx, const uint32_t* input_index, const uint8_t* scripts,
+               const uint32_t* script_off, const uint64_t* amount, const uint32_t* hashtype, uint8_t* tx_status,
+               uint8_t* hashes, uint8_t* status);
 
 /* ---- block headers on the GPU: the Equihash solution, the block hash and the
  * proof of work of HeaderVerifier::check (verification/src/verify_header.rs:26-32), batched. Any n

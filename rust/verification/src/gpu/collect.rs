@@ -27,8 +27,8 @@ use std::convert::TryInto;
 use std::sync::Arc;
 
 use super::cpu::CpuBackend;
-use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, Item};
-use super::ffi::{ZG_ECDSA_OK, ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
+use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, Item, SighashItem};
+use super::ffi::{ZG_ECDSA_OK, ZG_SIGHASH_OK, ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
                  ZG_PREP_KIND_OUTPUT, ZG_PREP_KIND_SPEND};
 use super::{ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_KIND_SPROUT, ZG_STATUS_OK};
 
@@ -83,6 +83,25 @@ pub struct EcdsaCheck {
     pub sighash: [u8; 32],
 }
 
+/// an EcdsaCheck whose sighash is still to be computed: what the checker would pass to
+/// TransactionInputSigner::signature_hash (script/src/sign.rs:152-160) -- the script code, the hashtype byte the
+/// signature carried and the amount of the output the input spends. Needs Tx::raw
+#[derive(Clone)]
+pub struct EcdsaRequest {
+    pub input_index: usize,
+    pub pubkey: Vec<u8>,
+    pub sig: Vec<u8>,
+    pub script_code: Vec<u8>,
+    pub hashtype: u32,
+    pub amount: u64,
+}
+
+/// lookup(input_index, pubkey, sig, script_code, hashtype) -> the verdict of a request's check: answerable
+/// without the host computing a sighash
+pub type RequestLookup<'a> = dyn FnMut(usize, &[u8], &[u8], &[u8], u32) -> Result<bool, GpuError> + 'a;
+/// eval_rerun for a transaction that carries ecdsa_requests
+pub type EvalRerunRequests = Arc<dyn Fn(&mut RequestLookup) -> Result<Option<TxError>, GpuError> + Send + Sync>;
+
 /// lookup(pubkey, sig, sighash) -> the signature check's verdict
 pub type EcdsaLookup<'a> = dyn FnMut(&[u8], &[u8], &[u8; 32]) -> Result<bool, GpuError> + 'a;
 /// the caller's second TransactionEval::check (accept_transaction.rs:363-422) with `lookup` as the
@@ -118,6 +137,14 @@ pub struct Tx {
     pub ecdsa_checks: Vec<EcdsaCheck>,
     /// ... otherwise this repeats the run with the real verdicts and its value is the eval error
     pub eval_rerun: Option<EvalRerun>,
+    /// the signature hashes on the GPU: the serialized transaction and its consensus
+    /// branch id. With raw set and sighash None, the no-input sighash (hashtype 1) is computed in the window's
+    /// ONE sighash call; ecdsa_requests are resolved to ecdsa_checks by the same call, and a transaction that
+    /// has requests is re-run through eval_rerun_requests
+    pub raw: Option<Vec<u8>>,
+    pub branch_id: u32,
+    pub ecdsa_requests: Vec<EcdsaRequest>,
+    pub eval_rerun_requests: Option<EvalRerunRequests>,
 }
 
 #[derive(Debug, Clone, PartialEq)]
@@ -144,6 +171,11 @@ pub trait Backend {
     fn ed25519_verify(&self, items: &[([u8; 32], [u8; 64], [u8; 32])]) -> Result<Vec<u8>, GpuError>;
     /// ECDSA statuses (ZG_ECDSA_*) for (public key, DER signature, 32-byte sighash)
     fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError>;
+    /// TransactionInputSigner::signature_hash per item over (serialized transaction, branch id) ->
+    /// (ZG_TX_* per transaction, hash per item, ZG_SIGHASH_* per item)
+    fn sighash(&self, _txs: &[(Vec<u8>, u32)], _items: &[SighashItem]) -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
+        Err(GpuError { code: -1, message: "this backend computes no signature hashes".to_string() })
+    }
     /// header statuses (ZG_HDR_*: the first failing of deserialize / Equihash / proof of work) for
     /// serialized 1487-byte headers against the compact `max_bits`
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError>;
@@ -173,6 +205,9 @@ impl Backend for GpuVerifier {
     }
     fn ecdsa_verify(&self, items: &[(Vec<u8>, Vec<u8>, [u8; 32])]) -> Result<Vec<u8>, GpuError> {
         GpuVerifier::ecdsa_verify(self, items)
+    }
+    fn sighash(&self, txs: &[(Vec<u8>, u32)], items: &[SighashItem]) -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
+        GpuVerifier::sighash(self, txs, items)
     }
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
         Ok(GpuVerifier::headers_verify(self, headers, max_bits)?.into_iter().map(|r| r.0).collect())
@@ -401,6 +436,65 @@ fn js_sig_verdicts<B: Backend>(v: &B, txs: &[Tx]) -> Result<Vec<bool>, GpuError>
 }
 
 type EcdsaKey = (Vec<u8>, Vec<u8>, [u8; 32]);
+/// (window index, input index or None, script code, hashtype) -> the sighash
+type SighashKey = (usize, Option<u32>, Vec<u8>, u32);
+
+/// one sighash call over the transactions `pairs` names; any status but ZG_SIGHASH_OK is an explicit error:
+/// the caller hashes that transaction on the host, it is never accepted silently
+fn run_sighash<B: Backend>(v: &B, txs: &[Tx], pairs: &[(usize, Option<u32>, Vec<u8>, u64, u32)]) -> Result<Vec<[u8; 32]>, GpuError> {
+    let mut idx: Vec<usize> = pairs.iter().map(|p| p.0).collect();
+    idx.sort();
+    idx.dedup();
+    let raws: Vec<(Vec<u8>, u32)> = idx.iter().map(|&i| (txs[i].raw.clone().unwrap_or_default(), txs[i].branch_id)).collect();
+    let items: Vec<SighashItem> = pairs
+        .iter()
+        .map(|p| SighashItem { tx: idx.binary_search(&p.0).unwrap() as u32, input_index: p.1, script_code: p.2.clone(), amount: p.3, hashtype: p.4 })
+        .collect();
+    let (_, hashes, status) = v.sighash(&raws, &items)?;
+    for (p, st) in pairs.iter().zip(&status) {
+        if *st != ZG_SIGHASH_OK {
+            return Err(GpuError { code: -1, message: format!("transaction {}: the signature hash of input {:?} was not computed (ZG_SIGHASH status {}); hash this transaction on the host", p.0, p.1, st) });
+        }
+    }
+    Ok(hashes)
+}
+
+/// the window with every sighash in place: transactions that carry raw bytes and lack their no-input sighash
+/// or carry ecdsa_requests are cloned with sighash set and the requests appended to ecdsa_checks, all from
+/// ONE sighash call; a window that uses neither field is returned as it is (None) and asks for no call
+fn resolve_sighashes<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(Vec<Tx>, HashMap<SighashKey, [u8; 32]>)>, GpuError> {
+    if let Some(i) = txs.iter().position(|t| t.raw.is_none() && !t.ecdsa_requests.is_empty()) {
+        return Err(GpuError { code: -1, message: format!("transaction {} carries ecdsa_requests but no raw bytes", i) });
+    }
+    let need: Vec<usize> =
+        (0..txs.len()).filter(|&i| txs[i].raw.is_some() && (txs[i].sighash.is_none() || !txs[i].ecdsa_requests.is_empty())).collect();
+    if need.is_empty() {
+        return Ok(None);
+    }
+    let mut pairs = Vec::new();
+    for &i in &need {
+        if txs[i].sighash.is_none() {
+            pairs.push((i, None, Vec::new(), 0u64, 1u32));
+        }
+        for r in &txs[i].ecdsa_requests {
+            pairs.push((i, Some(r.input_index as u32), r.script_code.clone(), r.amount, r.hashtype));
+        }
+    }
+    let hashes = run_sighash(v, txs, &pairs)?;
+    let known: HashMap<SighashKey, [u8; 32]> =
+        pairs.iter().zip(hashes).map(|(p, h)| ((p.0, p.1, p.2.clone(), p.4), h)).collect();
+    let mut out = txs.to_vec();
+    for &i in &need {
+        if out[i].sighash.is_none() {
+            out[i].sighash = Some(known[&(i, None, Vec::new(), 1u32)]);
+        }
+        for r in &txs[i].ecdsa_requests {
+            let sighash = known[&(i, Some(r.input_index as u32), r.script_code.clone(), r.hashtype)];
+            out[i].ecdsa_checks.push(EcdsaCheck { input_index: r.input_index, pubkey: r.pubkey.clone(), sig: r.sig.clone(), sighash });
+        }
+    }
+    Ok(Some((out, known)))
+}
 
 /// the verdict table of the window's recorded ECDSA checks: ONE ecdsa_verify call for all of them (any
 /// non-zero status is false, verify.rs:60-67 unwrap_or(false))
@@ -417,9 +511,42 @@ fn ecdsa_table<B: Backend>(v: &B, txs: &[Tx]) -> Result<HashMap<EcdsaKey, bool>,
 /// the eval error of one transaction: None when every recorded check is ZG_ECDSA_OK, else eval_rerun's
 /// value with the table as the checker; a triple the optimistic runs never asked for (OP_CHECKMULTISIG
 /// tries other pairs once one fails) is verified in a further call
-fn eval_error<B: Backend>(v: &B, tx: &Tx, table: &mut HashMap<EcdsaKey, bool>) -> Result<Option<TxError>, GpuError> {
+fn eval_error<B: Backend>(v: &B, txs: &[Tx], idx: usize, table: &mut HashMap<EcdsaKey, bool>,
+                          known: &mut HashMap<SighashKey, [u8; 32]>) -> Result<Option<TxError>, GpuError> {
+    let tx = &txs[idx];
     if tx.ecdsa_checks.iter().all(|c| table[&(c.pubkey.clone(), c.sig.clone(), c.sighash)]) {
         return Ok(None);
+    }
+    if !tx.ecdsa_requests.is_empty() {
+        let rerun = match &tx.eval_rerun_requests {
+            Some(r) => r.clone(),
+            None => return Err(GpuError { code: -1, message: "a transaction's requested ECDSA check failed but it carries no eval_rerun_requests".to_string() }),
+        };
+        // a request the optimistic run never made (another script code or pair): one further sighash call
+        // with the amount the input's other requests carry, then one further ecdsa_verify call
+        let mut lookup = |input: usize, pk: &[u8], sig: &[u8], code: &[u8], hashtype: u32| -> Result<bool, GpuError> {
+            let key = (idx, Some(input as u32), code.to_vec(), hashtype);
+            let sighash = match known.get(&key) {
+                Some(h) => *h,
+                None => {
+                    let amount = match tx.ecdsa_requests.iter().find(|r| r.input_index == input) {
+                        Some(r) => r.amount,
+                        None => return Err(GpuError { code: -1, message: format!("transaction {}: no amount is known for input {}", idx, input) }),
+                    };
+                    let h = run_sighash(v, txs, &[(idx, Some(input as u32), code.to_vec(), amount, hashtype)])?[0];
+                    known.insert(key, h);
+                    h
+                }
+            };
+            let k = (pk.to_vec(), sig.to_vec(), sighash);
+            if let Some(ok) = table.get(&k) {
+                return Ok(*ok);
+            }
+            let ok = v.ecdsa_verify(&[k.clone()])?[0] == ZG_ECDSA_OK;
+            table.insert(k, ok);
+            Ok(ok)
+        };
+        return (*rerun)(&mut lookup);
     }
     let rerun = match &tx.eval_rerun {
         Some(r) => r.clone(),
@@ -501,6 +628,16 @@ fn tx_error(tx: &Tx, plan: &(Vec<Plan>, Vec<Plan>, Vec<Plan>), status: &[u8], pg
 /// Ok(None) if every transaction passes, else Ok(Some((tx_index, error))) with the error the
 /// reference reports; Err only for a backend (GPU / runtime) failure.
 pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxError)>, GpuError> {
+    // the sighashes the window leaves to the backend (Tx::raw), before the signature batches
+    let resolved = resolve_sighashes(v, txs)?;
+    let (owned, mut known) = match resolved {
+        Some((t, k)) => (Some(t), k),
+        None => (None, HashMap::new()),
+    };
+    let txs: &[Tx] = match &owned {
+        Some(t) => &t[..],
+        None => txs,
+    };
     let (items, pghr, plans) = queue(v, txs)?;
     let status = if items.is_empty() { Vec::new() } else { v.verify(&items)? };
     let pghr_status = if pghr.is_empty() { Vec::new() } else { v.pghr13_verify(&pghr)? };
@@ -509,7 +646,7 @@ pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxEr
     let mut table = ecdsa_table(v, txs)?;
     for (idx, (tx, plan)) in txs.iter().zip(&plans).enumerate() {
         // precedence: pre_error, then the eval error, then the JoinSplit and Sapling stages
-        let eval = if tx.pre_error.is_none() && !tx.ecdsa_checks.is_empty() { eval_error(v, tx, &mut table)? } else { None };
+        let eval = if tx.pre_error.is_none() && !tx.ecdsa_checks.is_empty() { eval_error(v, txs, idx, &mut table, &mut known)? } else { None };
         if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx], js_ok[idx], eval) {
             return Ok(Some((idx, e)));
         }

@@ -29,6 +29,7 @@ use crypto::{pghr13_verify, Groth16VerifyingKey, Pghr13Proof, Pghr13VerifyingKey
 
 use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_MALFORMED, ZG_HDR_OK, ZG_HDR_POW};
 use super::ffi::{ZG_ECDSA_OK, ZG_ECDSA_PUBLIC, ZG_ECDSA_SIGNATURE, ZG_ECDSA_SIGNATURE_ENCODING};
+use super::ffi::{ZG_SIGHASH_INPUT_RANGE, ZG_SIGHASH_OK, ZG_SIGHASH_TX_MALFORMED, ZG_TX_MALFORMED, ZG_TX_OK};
 use super::ffi::{ZG_ED_OK, ZG_ED_PUBLIC_ENCODING, ZG_ED_SIGNATURE, ZG_ED_SIGNATURE_ENCODING, ZG_GEN_BINDING,
                  ZG_STATUS_INPUT_NONCANONICAL};
 use super::{GpuError, Item, ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_STATUS_DECODE_INVALID, ZG_STATUS_MALFORMED_VK,
@@ -165,6 +166,37 @@ impl<'a> super::collect::Backend for CpuBackend<'a> {
                 }
             })
             .collect())
+    }
+
+    /// the reference's own TransactionInputSigner::signature_hash (script/src/sign.rs:152-329) per item over
+    /// ser::deserialize of each transaction. A transaction that does not deserialize is ZG_TX_MALFORMED; the
+    /// reference reads and re-encodes non-minimal compact sizes, so nothing here is ZG_TX_NONCANONICAL; an
+    /// overwintered item whose index is past the inputs (the reference would panic) is ZG_SIGHASH_INPUT_RANGE
+    fn sighash(&self, txs: &[(Vec<u8>, u32)], items: &[super::SighashItem]) -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
+        let parsed: Vec<Option<::chain::Transaction>> =
+            txs.iter().map(|(raw, _)| ::ser::deserialize::<_, ::chain::Transaction>(&raw[..]).ok()).collect();
+        let tx_status: Vec<u8> = parsed.iter().map(|t| if t.is_some() { ZG_TX_OK } else { ZG_TX_MALFORMED }).collect();
+        let res: Vec<([u8; 32], u8)> = items
+            .par_iter()
+            .map(|it| {
+                let tx = match &parsed[it.tx as usize] {
+                    Some(t) => t,
+                    None => return ([0u8; 32], ZG_SIGHASH_TX_MALFORMED),
+                };
+                let index = it.input_index.map(|i| i as usize);
+                if tx.overwintered && index.map(|i| i >= tx.inputs.len()).unwrap_or(false) {
+                    return ([0u8; 32], ZG_SIGHASH_INPUT_RANGE);
+                }
+                let signer: ::script::TransactionInputSigner = tx.clone().into();
+                let mut cache = Default::default();
+                let script: ::script::Script = it.script_code.clone().into();
+                let hash = signer.signature_hash(&mut cache, index, it.amount, &script, it.hashtype, txs[it.tx as usize].1);
+                let mut out = [0u8; 32];
+                out.copy_from_slice(&hash[..]);
+                (out, ZG_SIGHASH_OK)
+            })
+            .collect();
+        Ok((tx_status, res.iter().map(|r| r.0).collect(), res.iter().map(|r| r.1).collect()))
     }
 
     /// crypto::verify_ed25519 for every (pubkey, signature, sighash), its error as ZG_ED_*

@@ -69,6 +69,16 @@ pub const ZG_ECDSA_PUBLIC: u8 = 1;
 pub const ZG_ECDSA_SIGNATURE_ENCODING: u8 = 2;
 pub const ZG_ECDSA_SIGNATURE: u8 = 3;
 pub const ZG_ECDSA_PUBKEY_STRIDE: usize = 65;
+// zg_tx_layout / zg_sighash: the parser's verdict on a transaction, an item's status, and the input index
+// that stands for the reference's None
+pub const ZG_TX_OK: u8 = 0;
+pub const ZG_TX_MALFORMED: u8 = 1;
+pub const ZG_TX_NONCANONICAL: u8 = 2;
+pub const ZG_SIGHASH_OK: u8 = 0;
+pub const ZG_SIGHASH_TX_MALFORMED: u8 = 1;
+pub const ZG_SIGHASH_TX_NONCANONICAL: u8 = 2;
+pub const ZG_SIGHASH_INPUT_RANGE: u8 = 3;
+pub const ZG_SIGHASH_NO_INPUT: u32 = 0xFFFF_FFFF;
 // zg_equihash_verify instances, zg_headers_verify statuses (the first failing check) and flags (every check)
 pub const ZG_EQ_200_9: c_int = 0;
 pub const ZG_EQ_96_5: c_int = 1;
@@ -149,6 +159,11 @@ extern "C" {
                              status: *mut u8) -> c_int;
     pub fn zg_ecdsa_verify(ctx: *mut ZgCtx, n: usize, pubkeys: *const u8, pubkey_len: *const u8, sigs: *const u8,
                            sig_off: *const u32, msg: *const u8, status: *mut u8) -> c_int;
+    pub fn zg_tx_layout(tx: *const u8, len: usize, out: *mut u64) -> c_int;
+    pub fn zg_sighash(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64, tx_branch_id: *const u32,
+                      n: usize, item_tx: *const u32, input_index: *const u32, scripts: *const u8,
+                      script_off: *const u32, amount: *const u64, hashtype: *const u32, tx_status: *mut u8,
+                      hashes: *mut u8, status: *mut u8) -> c_int;
     pub fn zg_last_sig_kernel_ms(ctx: *mut ZgCtx, ms: *mut f32) -> c_int;
     pub fn zg_equihash_verify(ctx: *mut ZgCtx, params: c_int, n: usize, inputs: *const u8, input_len: usize,
                               solutions: *const u8, ok: *mut u8, repeated: *mut u8) -> c_int;

@@ -35,6 +35,28 @@ pub struct Item {
     pub inputs: Vec<[u8; 32]>,
 }
 
+/// One signature hash to compute (GpuVerifier::sighash): the arguments of
+/// TransactionInputSigner::signature_hash (script/src/sign.rs:152-160) over transaction number `tx` of the call.
+#[derive(Clone, Debug, PartialEq, Eq, Hash)]
+pub struct SighashItem {
+    pub tx: u32,
+    pub input_index: Option<u32>,
+    pub script_code: Vec<u8>,
+    pub amount: u64,
+    pub hashtype: u32,
+}
+
+/// zg_tx_layout: the parser's verdict (ffi::ZG_TX_*) on one serialized transaction and, unless it is
+/// MALFORMED, [header word, inputs, outputs, JoinSplits, Sapling spends, Sapling outputs, signature
+/// version, bytes consumed]. CPU, no context.
+pub fn tx_layout(raw: &[u8]) -> (u8, [u64; 8]) {
+    let mut out = [0u64; 8];
+    let pad = [0u8; 1];
+    let p = if raw.is_empty() { pad.as_ptr() } else { raw.as_ptr() };
+    let rc = unsafe { ffi::zg_tx_layout(p, raw.len(), out.as_mut_ptr()) };
+    (rc as u8, out)
+}
+
 /// One batch slot on one GPU (device buffers only; the streams and the prepared verifying keys
 /// are shared per device inside libzg). Several slots keep several windows in flight.
 pub struct GpuVerifier {
@@ -221,6 +243,55 @@ impl GpuVerifier {
                                  status.as_mut_ptr())
         })?;
         Ok(status)
+    }
+
+    /// TransactionInputSigner::signature_hash (script/src/sign.rs:152-329) of every item over the serialized
+    /// transactions `txs` (raw bytes, consensus branch id). An item: the transaction's number, the input
+    /// index (None as the reference's None), the script code, the input's amount, the hashtype.
+    /// -> (ZG_TX_* per transaction, the 32-byte hash per item in H256 storage order, ZG_SIGHASH_* per item).
+    /// A hash is zero unless its status is ZG_SIGHASH_OK.
+    pub fn sighash(&self, txs: &[(Vec<u8>, u32)], items: &[SighashItem])
+                   -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let (ntx, n) = (txs.len(), items.len());
+        let mut arena = Vec::new();
+        let mut tx_off = Vec::with_capacity(ntx + 1);
+        let mut branch = Vec::with_capacity(ntx + 1);
+        for (raw, b) in txs.iter() {
+            tx_off.push(arena.len() as u64);
+            arena.extend_from_slice(raw);
+            branch.push(*b);
+        }
+        tx_off.push(arena.len() as u64);
+        arena.push(0);
+        branch.push(0);
+        let mut scripts = Vec::new();
+        let mut script_off = Vec::with_capacity(n + 1);
+        for it in items.iter() {
+            script_off.push(scripts.len() as u32);
+            scripts.extend_from_slice(&it.script_code);
+        }
+        if scripts.len() > u32::max_value() as usize {
+            return Err(GpuError { code: -1, message: "sighash: the script codes exceed 4 GiB".to_string() });
+        }
+        script_off.push(scripts.len() as u32);
+        scripts.push(0);
+        let item_tx: Vec<u32> = items.iter().map(|it| it.tx).chain(Some(0)).collect();
+        let index: Vec<u32> = items.iter().map(|it| it.input_index.unwrap_or(ffi::ZG_SIGHASH_NO_INPUT)).chain(Some(0)).collect();
+        let amount: Vec<u64> = items.iter().map(|it| it.amount).chain(Some(0)).collect();
+        let hashtype: Vec<u32> = items.iter().map(|it| it.hashtype).chain(Some(0)).collect();
+        let mut tx_status = vec![0u8; ntx + 1];
+        let mut hashes = vec![0u8; 32 * n + 1];
+        let mut status = vec![0u8; n + 1];
+        check(self.ctx, unsafe {
+            ffi::zg_sighash(self.ctx, ntx, arena.as_ptr(), tx_off.as_ptr(), branch.as_ptr(), n, item_tx.as_ptr(),
+                            index.as_ptr(), scripts.as_ptr(), script_off.as_ptr(), amount.as_ptr(), hashtype.as_ptr(),
+                            tx_status.as_mut_ptr(), hashes.as_mut_ptr(), status.as_mut_ptr())
+        })?;
+        tx_status.truncate(ntx);
+        status.truncate(n);
+        let hs = (0..n).map(|i| { let mut h = [0u8; 32]; h.copy_from_slice(&hashes[32 * i..32 * i + 32]); h }).collect();
+        Ok((tx_status, hs, status))
     }
 
     /// verify_equihash_solution (equihash.rs:80-172) for the instance `params` (ffi::ZG_EQ_*): per item

@@ -26,7 +26,11 @@ interpreter of the transparent inputs stays with the caller too, but the secp256
 under it can be handed in (Tx.ecdsa_checks, SURVEY.md 8(f) f7): the caller runs TransactionEval::check
 (accept_transaction.rs:363-422) once with a recording checker that answers true, every recorded check
 of the window is verified in ONE zg_ecdsa_verify call, and only a transaction with a failed check has
-its script run repeated with the real verdicts (Tx.eval_rerun). The collector prepares every public input of
+its script run repeated with the real verdicts (Tx.eval_rerun). The signature hashes themselves can be left to
+the GPU as well: a transaction that carries its serialized bytes (Tx.raw, Tx.branch_id) and
+no sighash gets the no-input hash the acceptor computes (accept_transaction.rs:374-386), and its checks may be
+handed in without their hash (Tx.ecdsa_requests: script code, hashtype and amount instead); all of the window's
+are computed in ONE zg_sighash call before the signature batches. The collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
 verifies all Groth16 proofs of the window in
@@ -92,6 +96,20 @@ class EcdsaCheck:
 
 
 @dataclass
+class EcdsaRequest:
+    """an EcdsaCheck whose sighash is still to be computed: the arguments the checker would pass to
+    TransactionInputSigner::signature_hash (script/src/verify.rs:60-67, sign.rs:152-160) -- the script code after
+    OP_CODESEPARATOR / signature removal, the hashtype byte the signature carried (as u32) and the amount of
+    the output the input spends. Needs Tx.raw"""
+    input_index: int
+    pubkey: bytes
+    sig: bytes
+    script_code: bytes
+    hashtype: int
+    amount: int
+
+
+@dataclass
 class Tx:
     """the shielded-proof view of one transaction, with the caller's non-Groth16 outcomes"""
     pre_error: Optional[str] = None           # first failing check before the JoinSplit stage
@@ -119,6 +137,13 @@ class Tx:
     # checker and returns the reference's eval error, or None
     ecdsa_checks: List[EcdsaCheck] = field(default_factory=list)
     eval_rerun: Optional[Callable] = None
+    # the signature hashes on the GPU: the serialized transaction and its consensus
+    # branch id. With raw set and sighash None, the no-input sighash (hashtype 1) is computed in the window's
+    # zg_sighash call; ecdsa_requests are resolved to ecdsa_checks by the same call. eval_rerun of a transaction
+    # with requests may ask lookup(input_index, pubkey, sig, script_code, hashtype) -> bool: no sighash needed
+    raw: Optional[bytes] = None
+    branch_id: Optional[int] = None
+    ecdsa_requests: List[EcdsaRequest] = field(default_factory=list)
 
 
 _POOL = None
@@ -324,7 +349,64 @@ def _js_sig_verdicts(txs, ctx, verify_js_sigs):
     return ok
 
 
-def _eval_errors(txs, ctx, verify_ecdsa):
+def _resolve_sighashes(txs, ctx, sighash):
+    """-> (txs with every sighash in place, resolve). The transactions that carry raw bytes and lack their
+    no-input sighash or carry ecdsa_requests are copied with sighash set and the requests appended to
+    ecdsa_checks as EcdsaChecks, all from ONE sighash(raws, branch_ids, items) call (default ctx.sighash);
+    the others are passed through untouched. resolve(i, input_index, script_code, hashtype) -> the sighash of
+    a request of transaction i (computed by a further call if the window's did not hold it). A transaction
+    or item the GPU does not hash (a status other than SIGHASH_OK) raises: the caller hashes it."""
+    need = [i for i, tx in enumerate(txs) if tx.raw is not None and (tx.sighash is None or tx.ecdsa_requests)]
+    bad = [i for i, tx in enumerate(txs) if tx.raw is None and tx.ecdsa_requests]
+    if bad:
+        raise zg.ZgError(-1, "transaction %d carries ecdsa_requests but no raw bytes" % bad[0])
+    if not need:
+        return txs, None
+    if sighash is None:
+        if ctx is None:
+            raise zg.ZgError(-1, "transactions carry raw bytes but no sighash backend was given (pass ctx= or sighash=)")
+        sighash = ctx.sighash
+    from dataclasses import replace
+
+    def run(pairs):
+        """pairs: (window index, (input index | None, script code, amount, hashtype)) -> hashes"""
+        idx = sorted({i for i, _ in pairs})
+        pos = {i: k for k, i in enumerate(idx)}
+        _, hashes, status = sighash([bytes(txs[i].raw) for i in idx], [txs[i].branch_id or 0 for i in idx],
+                                    [(pos[i],) + tuple(it) for i, it in pairs])
+        for (i, it), st in zip(pairs, status):
+            if st != zg.SIGHASH_OK:
+                raise zg.ZgError(-1, "transaction %d: the signature hash of input %r was not computed (ZG_SIGHASH "
+                                     "status %d); hash this transaction on the host" % (i, it[0], st))
+        return hashes
+
+    pairs = []
+    for i in need:
+        if txs[i].sighash is None:
+            pairs.append((i, (None, b"", 0, 1)))
+        pairs += [(i, (r.input_index, bytes(r.script_code), r.amount, r.hashtype)) for r in txs[i].ecdsa_requests]
+    known = {(i, it[0], it[1], it[3]): h for (i, it), h in zip(pairs, run(pairs))}
+    out = list(txs)
+    for i in need:
+        tx = txs[i]
+        checks = list(tx.ecdsa_checks) + [
+            EcdsaCheck(r.input_index, r.pubkey, r.sig, known[(i, r.input_index, bytes(r.script_code), r.hashtype)])
+            for r in tx.ecdsa_requests]
+        out[i] = replace(tx, sighash=tx.sighash if tx.sighash is not None else known[(i, None, b"", 1)],
+                         ecdsa_checks=checks)
+
+    def resolve(i, input_index, script_code, hashtype):
+        key = (i, input_index, bytes(script_code), hashtype)
+        if key not in known:
+            amounts = {r.amount for r in txs[i].ecdsa_requests if r.input_index == input_index}
+            if len(amounts) != 1:
+                raise zg.ZgError(-1, "transaction %d: no single amount is known for input %d" % (i, input_index))
+            known[key] = run([(i, (input_index, key[2], amounts.pop(), hashtype))])[0]
+        return known[key]
+    return out, resolve
+
+
+def _eval_errors(txs, ctx, verify_ecdsa, resolve=None):
     """-> eval_error(tx): the reference's TransactionEval error of a transaction (None: the scripts pass).
     Every recorded check of the window goes through ONE verify_ecdsa call; a transaction whose checks are
     all ECDSA_OK has no eval error (its optimistic run was the reference's run); for any other one the
@@ -349,12 +431,23 @@ def _eval_errors(txs, ctx, verify_ecdsa):
             table[k] = verify_ecdsa([k[0]], [k[1]], [k[2]])[0] == zg.ECDSA_OK
         return table[k]
 
+    where = {id(tx): i for i, tx in enumerate(txs)}
+
     def eval_error(tx):
         if all(table[(bytes(c.pubkey), bytes(c.sig), bytes(c.sighash))] for c in tx.ecdsa_checks):
             return None
         if tx.eval_rerun is None:
             raise zg.ZgError(-1, "a transaction's ECDSA check failed but it carries no eval_rerun")
-        return tx.eval_rerun(lookup)
+        if not tx.ecdsa_requests:
+            return tx.eval_rerun(lookup)
+
+        def lookup_request(*key):
+            """(pubkey, sig, sighash), or (input_index, pubkey, sig, script_code, hashtype) of a request"""
+            if len(key) == 3:
+                return lookup(*key)
+            input_index, pubkey, sig, script_code, hashtype = key
+            return lookup(pubkey, sig, resolve(where[id(tx)], input_index, script_code, hashtype))
+        return tx.eval_rerun(lookup_request)
     return eval_error
 
 
@@ -418,7 +511,7 @@ def _chunked(verify, cap):
 
 
 def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
-                 verify_js_sigs=None, verify_ecdsa=None):
+                 verify_js_sigs=None, verify_ecdsa=None, sighash=None):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -436,7 +529,12 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     ECDSA checks of the transparent inputs (Tx.ecdsa_checks) go through verify_ecdsa(pubkeys, sigs,
     msgs) -> ECDSA_* statuses, default ctx.ecdsa_verify (ONE zg_ecdsa_verify call for the window); the
     eval error of a transaction with a failed check is its eval_rerun's, placed after pre_error and
-    before the JoinSplit and Sapling stages (accept_transaction.rs:68-84)."""
+    before the JoinSplit and Sapling stages (accept_transaction.rs:68-84). Transactions that carry their
+    serialized bytes (Tx.raw, Tx.branch_id) get the sighashes they lack -- the no-input one, and one per
+    Tx.ecdsa_requests entry -- from sighash(raws, branch_ids, items) -> (tx statuses, hashes, statuses),
+    default ctx.sighash (ONE zg_sighash call for the window, before the signature batches); a transaction
+    the GPU reports as malformed or non-canonical raises ZgError and is the caller's to hash."""
+    txs, resolve = _resolve_sighashes(txs, ctx, sighash)
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:
         def verify(proofs, kinds, inputs, n_inputs):
@@ -461,7 +559,7 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
         pghr_status = list(verify_pghr([p for p, _ in pghr], [inp for _, inp in pghr]))
     sp_ok, bind_ok = _sig_verdicts(txs, ctx, verify_sigs, sapling_bvk)
     js_ok = _js_sig_verdicts(txs, ctx, verify_js_sigs)
-    eval_error = _eval_errors(txs, ctx, verify_ecdsa)
+    eval_error = _eval_errors(txs, ctx, verify_ecdsa, resolve)
     for idx, (tx, plan) in enumerate(zip(txs, plans)):
         err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx], eval_error)
         if err is not None:

@@ -22,6 +22,7 @@
 #include "zg_kernels.h"
 #include "zg_msm.h"
 #include "zg_prep.h"
+#include "zg_sighash.h"
 #include "zg_vk_embed.h"  // generated from zebra_amd/res/*.json by zebra_amd/build.py
 
 using namespace zg;
@@ -813,6 +814,11 @@ hipError_t launch_ecdsa(hipStream_t st, const uint8_t* pubkeys, const uint8_t* p
                         const uint32_t* sig_off, const uint8_t* msg, int n, const uint32_t* comb, uint8_t* status);
 hipError_t launch_ed25519(hipStream_t st, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg, int n,
                           const uint32_t* comb, uint8_t* status);
+hipError_t launch_sighash_digests(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
+                                  const uint32_t* out_off, const uint32_t* jobs, int njobs, uint8_t* digests);  // zg_sighash.hip
+hipError_t launch_sighash_items(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
+                                const uint32_t* out_off, const uint8_t* digests, const uint8_t* scripts,
+                                const ShDevItem* items, int n, uint8_t* hashes);
 int equihash_solution_bytes(int params);                                                      // zg_equihash.hip
 hipError_t launch_equihash(hipStream_t st, int params, const uint8_t* inputs, size_t in_stride, int in_len,
                            const uint8_t* sols, size_t sol_stride, int n, uint8_t* ok, uint8_t* repeated);
@@ -1714,6 +1720,119 @@ extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, co
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ signature hashes (zg_sighash.h)
+extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                          const uint32_t* tx_branch_id, size_t n, const uint32_t* item_tx, const uint32_t* input_index,
+                          const uint8_t* scripts, const uint32_t* script_off, const uint64_t* amount,
+                          const uint32_t* hashtype, uint8_t* tx_status, uint8_t* hashes, uint8_t* status) {
+  if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status)) ||
+      (n && (!item_tx || !input_index || !scripts || !script_off || !amount || !hashtype || !hashes || !status)) ||
+      ntx > (1u << 30) || n > (1u << 30))
+    return ZG_E_INVAL;
+  for (size_t t = 0; t < ntx; t++)
+    if (tx_off[t + 1] < tx_off[t]) return ZG_E_INVAL;
+  if (ntx && tx_off[ntx] - tx_off[0] > (1ull << 31)) return ZG_E_INVAL;
+  for (size_t i = 0; i < n; i++)
+    if (script_off[i + 1] < script_off[i] || item_tx[i] >= ntx) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!ntx && !n) return ZG_OK;
+
+  // the layouts: every offset a lane follows is checked here
+  const uint64_t base0 = ntx ? tx_off[0] : 0;
+  std::vector<ShDevTx> dtx(ntx ? ntx : 1);
+  std::vector<uint32_t> in_off, out_off;
+  for (size_t t = 0; t < ntx; t++) {
+    ShDevTx& d = dtx[t];
+    tx_status[t] = (uint8_t)tx_parse(txs + tx_off[t], (size_t)(tx_off[t + 1] - tx_off[t]), d.L, in_off, out_off);
+    d.base = (uint32_t)(tx_off[t] - base0);
+    d.branch_id = tx_branch_id[t];
+    d.dig = 0;
+  }
+  // the items a lane takes, and the digests they read
+  std::vector<ShDevItem> items;
+  std::vector<uint64_t> cost;
+  std::vector<uint8_t> need(ntx ? ntx : 1, 0);
+  items.reserve(n);
+  for (size_t i = 0; i < n; i++) {
+    const ShDevTx& d = dtx[item_tx[i]];
+    const TxLayout& L = d.L;
+    const uint8_t ts = tx_status[item_tx[i]];
+    memset(hashes + 32 * i, 0, 32);
+    status[i] = ts == ZG_TX_MALFORMED ? ZG_SIGHASH_TX_MALFORMED : ts == ZG_TX_NONCANONICAL ? ZG_SIGHASH_TX_NONCANONICAL
+              : L.sigver && input_index[i] != ZG_SIGHASH_NO_INPUT && input_index[i] >= L.n_in ? ZG_SIGHASH_INPUT_RANGE
+                                                                                             : ZG_SIGHASH_OK;
+    if (status[i] != ZG_SIGHASH_OK) continue;
+    const uint32_t base = sh_base(hashtype[i]), acp = hashtype[i] & 0x80;
+    const uint32_t slen = script_off[i + 1] - script_off[i];
+    if (!L.sigver && input_index[i] >= L.n_in && (acp || base == SH_SINGLE)) continue;  // the zero hash, OK
+    items.push_back(ShDevItem{item_tx[i], input_index[i], script_off[i] - script_off[0], slen, hashtype[i], (uint32_t)i,
+                              amount[i]});
+    if (L.sigver) {
+      need[item_tx[i]] |= (uint8_t)((acp ? 0 : 1 << SH_PREVOUTS) | (!acp && base == SH_ALL ? 1 << SH_SEQUENCES : 0) |
+                                    (base == SH_ALL ? 1 << SH_OUTPUTS : 0) | (L.n_js ? 1 << SH_JOINSPLITS : 0) |
+                                    (L.sigver == 2 && L.n_spend ? 1 << SH_SPENDS : 0) |
+                                    (L.sigver == 2 && L.n_sout ? 1 << SH_SOUTPUTS : 0));
+      cost.push_back(2 * (uint64_t)(512 + slen));  // a BLAKE2b compression per 128 bytes, about two SHA-256 ones
+    } else {
+      cost.push_back(acp ? 256 + (uint64_t)slen + L.consumed - L.lock_off : (uint64_t)L.consumed + slen);
+    }
+  }
+  std::vector<uint32_t> order(items.size());
+  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
+  std::vector<ShDevItem> sorted(items.size() ? items.size() : 1);
+  for (size_t k = 0; k < order.size(); k++) sorted[k] = items[order[k]];
+  std::vector<uint32_t> jobs;
+  uint32_t ndig = 0;
+  for (size_t t = 0; t < ntx; t++)
+    if (need[t]) {
+      dtx[t].dig = ndig++;
+      for (int w = 0; w < SH_DIGESTS; w++)
+        if (need[t] >> w & 1) jobs.push_back((uint32_t)(t << 3) | (uint32_t)w);
+    }
+  const size_t m = items.size();
+  if (!m) return ZG_OK;
+
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0), script_bytes = (size_t)script_off[n] - script_off[0];
+  DevScratch s;
+  uint8_t *darena, *dscripts, *ddig, *dhash;
+  ShDevTx* dtxs;
+  ShDevItem* ditems;
+  uint32_t *din, *dout, *djobs;
+  HIPCHK(s.alloc(&darena, arena_bytes + 8));
+  HIPCHK(s.alloc(&dscripts, script_bytes + 8));
+  HIPCHK(s.alloc(&ddig, (size_t)32 * SH_DIGESTS * (ndig ? ndig : 1)));
+  HIPCHK(s.alloc(&dhash, 32 * m));
+  HIPCHK(s.alloc(&dtxs, sizeof(ShDevTx) * ntx));
+  HIPCHK(s.alloc(&ditems, sizeof(ShDevItem) * m));
+  HIPCHK(s.alloc(&din, sizeof(uint32_t) * (in_off.size() + 1)));
+  HIPCHK(s.alloc(&dout, sizeof(uint32_t) * (out_off.size() + 1)));
+  HIPCHK(s.alloc(&djobs, sizeof(uint32_t) * (jobs.size() + 1)));
+  HIPCHK(hipMemcpyAsync(darena, txs + base0, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (script_bytes)
+    HIPCHK(hipMemcpyAsync(dscripts, scripts + script_off[0], script_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dtxs, dtx.data(), sizeof(ShDevTx) * ntx, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ditems, sorted.data(), sizeof(ShDevItem) * m, hipMemcpyHostToDevice, ctx->stream));
+  if (!in_off.empty())
+    HIPCHK(hipMemcpyAsync(din, in_off.data(), sizeof(uint32_t) * in_off.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!out_off.empty())
+    HIPCHK(hipMemcpyAsync(dout, out_off.data(), sizeof(uint32_t) * out_off.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!jobs.empty())
+    HIPCHK(hipMemcpyAsync(djobs, jobs.data(), sizeof(uint32_t) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_events(ctx));
+  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
+  HIPCHK(launch_sighash_digests(ctx->stream, darena, dtxs, din, dout, djobs, (int)jobs.size(), ddig));
+  HIPCHK(launch_sighash_items(ctx->stream, darena, dtxs, din, dout, ddig, dscripts, ditems, (int)m, dhash));
+  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  std::vector<uint8_t> hh(32 * m);
+  HIPCHK(hipMemcpyAsync(hh.data(), dhash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * sorted[k].slot, hh.data() + 32 * k, 32);
   return ZG_OK;
 }
 

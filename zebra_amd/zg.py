@@ -20,6 +20,11 @@ ED_OK, ED_PUBLIC_ENCODING, ED_SIGNATURE_ENCODING, ED_SIGNATURE = 0, 1, 2, 3
 # Error::InvalidSignature, Ok(false)); the stride of one key in zg_ecdsa_verify's pubkeys
 ECDSA_OK, ECDSA_PUBLIC, ECDSA_SIGNATURE_ENCODING, ECDSA_SIGNATURE = 0, 1, 2, 3
 ECDSA_PUBKEY_STRIDE = 65
+# include/zg.h ZG_TX_* (zg_tx_layout's verdict on a serialized transaction), ZG_SIGHASH_* (an item of zg_sighash) and
+# the input index that stands for the reference's None
+TX_OK, TX_MALFORMED, TX_NONCANONICAL = 0, 1, 2
+SIGHASH_OK, SIGHASH_TX_MALFORMED, SIGHASH_TX_NONCANONICAL, SIGHASH_INPUT_RANGE = 0, 1, 2, 3
+SIGHASH_NO_INPUT = 0xFFFFFFFF
 # include/zg.h ZG_EQ_* (Equihash instances), ZG_HDR_* (the first failing header check) and ZG_HDR_F_* (every check)
 EQ_200_9, EQ_96_5, EQ_48_5 = 0, 1, 2
 EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
@@ -90,6 +95,10 @@ def lib():
         L.zg_redjubjub_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p, u8p]
         L.zg_ed25519_verify.argtypes = [vp, sz, u8p, u8p, u8p, u8p]
         L.zg_ecdsa_verify.argtypes = [vp, sz, u8p, u8p, u8p, ctypes.POINTER(ctypes.c_uint32), u8p, u8p]
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        L.zg_tx_layout.argtypes = [u8p, sz, ctypes.POINTER(ctypes.c_uint64)]
+        L.zg_sighash.argtypes = [vp, sz, u8p, ctypes.POINTER(ctypes.c_uint64), u32p, sz, u32p, u32p, u8p, u32p,
+                                 ctypes.POINTER(ctypes.c_uint64), u32p, u8p, u8p, u8p]
         L.zg_last_sig_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.zg_equihash_verify.argtypes = [vp, ctypes.c_int, sz, u8p, sz, u8p, u8p, u8p]
         L.zg_headers_verify.argtypes = [vp, sz, u8p, ctypes.c_uint32, u8p, u8p, u8p]
@@ -235,6 +244,47 @@ def pack_ecdsa(pubkeys, sigs, msgs):
     if total >= 1 << 32:
         raise ZgError(-1, "ecdsa_verify: the signatures exceed 4 GiB")
     return keys, lens, b"".join(map(bytes, sigs)), off, b"".join(map(bytes, msgs))
+
+
+def tx_layout(raw):
+    """zg_tx_layout: Transaction::deserialize (chain/src/transaction.rs:249-330) over exactly these bytes ->
+    (TX_* status, [header word, inputs, outputs, JoinSplits, Sapling spends, Sapling outputs, signature version,
+    bytes consumed]); the list is zero when the status is TX_MALFORMED. CPU, no context"""
+    out = (ctypes.c_uint64 * 8)()
+    rc = lib().zg_tx_layout(bytes(raw) + b"\0", len(raw), out)
+    if rc < 0:
+        raise ZgError(rc, "zg_tx_layout")
+    return rc, list(out)
+
+
+def pack_sighash(txs, branch_ids, items):
+    """the buffers of zg_sighash. txs: serialized transactions; branch_ids: one consensus branch id per
+    transaction; items: (transaction number, input index or None, script code, amount, hashtype) ->
+    (arena, tx_off, branch, item_tx, input_index, scripts, script_off, amount, hashtype), the arrays as ctypes"""
+    ntx, n = len(txs), len(items)
+    if len(branch_ids) != ntx:
+        raise ZgError(-1, "sighash takes one branch id per transaction")
+    tx_off = (ctypes.c_uint64 * (ntx + 1))()
+    total = 0
+    for t, raw in enumerate(txs):
+        tx_off[t] = total
+        total += len(raw)
+    tx_off[ntx] = total
+    branch = (ctypes.c_uint32 * max(ntx, 1))(*[b & 0xFFFFFFFF for b in branch_ids])
+    item_tx = (ctypes.c_uint32 * max(n, 1))(*[it[0] for it in items])
+    index = (ctypes.c_uint32 * max(n, 1))(*[SIGHASH_NO_INPUT if it[1] is None else it[1] for it in items])
+    script_off = (ctypes.c_uint32 * (n + 1))()
+    stotal = 0
+    for i, it in enumerate(items):
+        script_off[i] = stotal
+        stotal += len(it[2])
+    if stotal >= 1 << 32:
+        raise ZgError(-1, "sighash: the script codes exceed 4 GiB")
+    script_off[n] = stotal
+    amount = (ctypes.c_uint64 * max(n, 1))(*[it[3] for it in items])
+    hashtype = (ctypes.c_uint32 * max(n, 1))(*[it[4] & 0xFFFFFFFF for it in items])
+    return (b"".join(map(bytes, txs)), tx_off, branch, item_tx, index, b"".join(bytes(it[2]) for it in items),
+            script_off, amount, hashtype)
 
 
 def pow_valid(max_bits, bits, hash32):
@@ -471,9 +521,23 @@ class Context:
         self._chk(lib().zg_ecdsa_verify(self._p, n, keys, lens, sg + b"\0", off, msg, st))
         return list(st.raw[:n])
 
+    def sighash(self, txs, branch_ids, items):
+        """TransactionInputSigner::signature_hash (script/src/sign.rs:152-329) per item over the serialized
+        transactions. items: (transaction number, input index or None, script code, amount, hashtype) ->
+        (TX_* per transaction, 32-byte hash per item in H256 storage order, SIGHASH_* per item); a hash is zero
+        unless its status is SIGHASH_OK"""
+        ntx, n = len(txs), len(items)
+        arena, tx_off, branch, item_tx, index, scripts, script_off, amount, hashtype = pack_sighash(txs, branch_ids, items)
+        ts = ctypes.create_string_buffer(max(ntx, 1))
+        hs = ctypes.create_string_buffer(max(32 * n, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._chk(lib().zg_sighash(self._p, ntx, arena + b"\0", tx_off, branch, n, item_tx, index, scripts + b"\0",
+                                   script_off, amount, hashtype, ts, hs, st))
+        return list(ts.raw[:ntx]), [hs.raw[32 * i:32 * i + 32] for i in range(n)], list(st.raw[:n])
+
     def last_sig_kernel_ms(self):
         """device time of the kernel(s) of the last ed25519_verify / ecdsa_verify / redjubjub_verify /
-        equihash_verify / headers_verify call"""
+        equihash_verify / headers_verify / sighash call"""
         ms = ctypes.c_float(0)
         self._chk(lib().zg_last_sig_kernel_ms(self._p, ctypes.byref(ms)))
         return ms.value
