@@ -6,6 +6,7 @@
 #include "../../zebra_amd/csrc/zg_groth16.h"
 #include "../../zebra_amd/csrc/zg_bingcd.h"
 #include "../../zebra_amd/csrc/zg_bn254.h"
+#include "../../zebra_amd/csrc/zg_jubjub.h"
 #include "../../zebra_amd/csrc/zg_lines.h"
 #include "../../zebra_amd/csrc/zg_msm.h"
 
@@ -299,6 +300,20 @@ void zgt_batch_scalar(const uint8_t* r16, uint8_t* out) {
   batch_scalar_ab(r16, &a, &b);
   Fr v = fr_from_mont(batch_scalar_fr(a, b));
   memcpy(out, v.l, 32);
+}
+// the sign rule of every decoded point: y > -y for a canonical y (48-byte BE; Fq2 as c0 || c1)
+int zgt_fq_lex_greatest(const uint8_t* y) { return fq_lex_greatest(ld_fq(y)); }
+int zgt_f2_lex_greatest(const uint8_t* y) {
+  const Fq2 v = {ld_fq(y), ld_fq(y + 48)};
+  return f2_lex_greatest(v);
+}
+// the kernels' edwards::Point::read (zg_jubjub.h jj_read): 1 and canonical LE x || y, or 0
+int zgt_jj_read(const uint8_t* in, uint8_t* xy) {
+  Fr x, y;
+  if (!jj_read(in, &x, &y)) return 0;
+  prep_fr_to_le(fr_from_mont(x), xy);
+  prep_fr_to_le(fr_from_mont(y), xy + 32);
+  return 1;
 }
 int zgt_g1_in_subgroup(const uint8_t* xy) { return g1_in_subgroup({ld_fq(xy), ld_fq(xy + 48), false}); }
 int zgt_g2_in_subgroup(const uint8_t* xy) {

@@ -142,6 +142,19 @@ def test_subgroup_checks(L):
             B.g2_in_subgroup((x, y)))
 
 
+def test_g2_subgroup_check_on_every_cofactor_part(L):
+    """g2_in_subgroup (the psi check) on a point of every prime part of G2's cofactor and on Q + T for each
+    (tests/decode_edges.g2_torsion_cases): a fast endomorphism check that is wrong typically accepts
+    exactly the points of one small torsion part, which random twist points almost never are"""
+    from tests import decode_edges as D
+    cases = D.g2_torsion_cases()
+    assert sum(1 for _, _, ok in cases if not ok) == 2 * len(D.H2_PARTS)
+    for nm, q, want in cases:
+        assert want == B.g2_in_subgroup(q)
+        got = L.zgt_g2_in_subgroup(b"".join(fq_b(v) for v in (q[0][0], q[0][1], q[1][0], q[1][1])))
+        assert got == int(want), nm
+
+
 def test_lazy_linear_forms(L):
     """zg_coop.h LazyAcc: any 384-bit terms, |c| < 128, <= 8 terms -> value mod p, < 2.2p
     (canon: < p); the extremes of the bounds included."""
