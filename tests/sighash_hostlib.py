@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "zg_hosttest_sighash.hip")
 LIB = os.path.join(HERE, "native", "libzg_hosttest_sighash.so")
 CSRC = os.path.join(ROOT, "zebra_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "zg_sighash.h"), os.path.join(CSRC, "zg_txparse.h")]
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("zg_sighash.h", "zg_hash.h", "zg_txparse.h")]
 HOST_FLAGS = ["-x", "hip", "--offload-host-only", "-std=c++17", "-Wno-psabi", "-pthread"]
 
 

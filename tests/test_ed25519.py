@@ -1,17 +1,31 @@
 """The Ed25519 JoinSplit signature check on the GPU (zg_ed25519_verify).
 
 CPU tier: the big-int restatement (tests/ed25519_ref.py) against RFC 8032 TEST 1 and the three
-real JoinSplit signatures of block 419221, every fixture status recomputed, and the collector's
-error precedence with injected verifiers.
+real JoinSplit signatures of block 419221, every fixture status recomputed, the kernel's own
+per-item routine compiled for the host (tests/native/zg_hosttest_ed25519.hip) bit-exact on every
+fixture and on the two debug products, and the collector's error precedence with injected
+verifiers.
 GPU tier: zg_ed25519_verify against the fixture statuses (bit-exact verdict and error class), the
 wave tail and second-block sizes, a 4,097-item batch with 1 % corrupted items, the field / scalar
 debug products, and the collector through a real context."""
+import ctypes
+import os
 import random
+import shutil
+import subprocess
 
 import pytest
 
 from tests import ed25519_ref as E
 from tests.conftest import load_golden
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+HOST_SRC = os.path.join(HERE, "native", "zg_hosttest_ed25519.hip")
+HOST_LIB = os.path.join(HERE, "native", "libzg_hosttest_ed25519.so")
+CSRC = os.path.join(ROOT, "zebra_amd", "csrc")
+
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 
 REAL_TX = {"53cf8971": "J2", "a2a2fe38": "J3", "70abe357": "J4"}   # tests/test_collector.py SRC_TX
 
@@ -37,6 +51,20 @@ def fixture_items():
 
 def run(ctx, items):
     return ctx.ed25519_verify([i[1] for i in items], [i[2] for i in items], [i[3] for i in items])
+
+
+def field_pairs(field):
+    """the operand pairs of the debug products (fields 5 and 6), shared by the host and the GPU test"""
+    edge = [0, 1, E.P - 1, E.P, 2 ** 255 - 1, 2 ** 256 - 1, E.L - 1, E.L]
+    rnd = random.Random(50 + field)
+    return [(a, b) for a in edge for b in edge] + [(rnd.randrange(2 ** 256), rnd.randrange(2 ** 256))
+                                                   for _ in range(256)]
+
+
+def check_products(field, pairs, got):
+    for (a, b), g in zip(pairs, got):
+        want = a * b % E.P if field == 5 else (a + (b << 256)) % E.L
+        assert int.from_bytes(g, "little") == want, (field, hex(a), hex(b))
 
 
 # ------------------------------------------------------------------ CPU tier
@@ -66,6 +94,44 @@ def test_fixture_statuses_recomputed():
     for name, st in want.items():
         assert got[name] == st, name
     assert "all_zero" in got
+
+
+_HOST = None
+
+
+def host_lib():
+    """the kernel's per-item routine and debug products compiled for the CPU (--offload-host-only),
+    built on demand like tests/hostlib.py"""
+    global _HOST
+    if _HOST is None:
+        deps = [HOST_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+        if not os.path.exists(HOST_LIB) or any(os.path.getmtime(d) > os.path.getmtime(HOST_LIB) for d in deps):
+            subprocess.check_call(["hipcc", "-x", "hip", "--offload-host-only", "-O2", "-fPIC", "-shared",
+                                   "-std=c++17", "-Wno-psabi", HOST_SRC, "-o", HOST_LIB])
+        _HOST = ctypes.CDLL(HOST_LIB)
+    return _HOST
+
+
+@needs_hipcc
+def test_host_compiled_kernel_routine_on_every_fixture():
+    items = fixture_items()
+    assert len(items) == 67
+    st = ctypes.create_string_buffer(len(items))
+    assert host_lib().zgt_ed25519_verify(ctypes.c_size_t(len(items)), b"".join(i[1] for i in items),
+                                         b"".join(i[2] for i in items), b"".join(i[3] for i in items), st) == 0
+    bad = [(i[0], i[4], g) for i, g in zip(items, st.raw) if g != i[4]]
+    assert not bad, bad
+
+
+@needs_hipcc
+@pytest.mark.parametrize("field", [5, 6])
+def test_host_compiled_field_products(field):
+    pairs = field_pairs(field)
+    out = ctypes.create_string_buffer(32 * len(pairs))
+    host_lib().zgt_ed25519_field_mul(field, ctypes.c_size_t(len(pairs)),
+                                     b"".join(a.to_bytes(32, "little") for a, _ in pairs),
+                                     b"".join(b.to_bytes(32, "little") for _, b in pairs), out)
+    check_products(field, pairs, [out.raw[32 * i:32 * i + 32] for i in range(len(pairs))])
 
 
 def real_window():
@@ -215,15 +281,10 @@ def test_gpu_corrupted_batch(ctx):
 @pytest.mark.parametrize("field", [5, 6])
 def test_gpu_debug_field_products(field):
     from zebra_amd import zg
-    edge = [0, 1, E.P - 1, E.P, 2 ** 255 - 1, 2 ** 256 - 1, E.L - 1, E.L]
-    rnd = random.Random(50 + field)
-    pairs = [(a, b) for a in edge for b in edge] + [(rnd.randrange(2 ** 256), rnd.randrange(2 ** 256))
-                                                    for _ in range(256)]
+    pairs = field_pairs(field)
     got = zg.debug_field_mul(field, [a.to_bytes(32, "little") for a, _ in pairs],
                              [b.to_bytes(32, "little") for _, b in pairs])
-    for (a, b), g in zip(pairs, got):
-        want = a * b % E.P if field == 5 else (a + (b << 256)) % E.L
-        assert int.from_bytes(g, "little") == want, (field, hex(a), hex(b))
+    check_products(field, pairs, got)
 
 
 @pytest.mark.gpu

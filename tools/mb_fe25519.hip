@@ -1,5 +1,5 @@
 // mb_fe25519.hip -- ISA count of the two candidate digit forms of the field 2^255 - 19:
-// 9 x 29-bit digits with the 2^261 = 1216 fold (zg_ed25519.h fe_mul / fe_sqr) against 10 x 25.5-bit
+// 9 x 29-bit digits with the 2^261 = 1216 fold (zg_fd9.h fd_mul / fd_sqr over Fe of zg_ed25519.h) against 10 x 25.5-bit
 // digits with 19 b pre-folded. Not run: compiled to assembly and counted.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 --offload-device-only -S -Izebra_amd/csrc -Iinclude
 //         -o mb_fe25519.s tools/mb_fe25519.hip, then count the instructions of each kernel
@@ -20,7 +20,7 @@ __device__ __forceinline__ void mul255(uint32_t* r, const uint32_t* f, const uin
     for (int i = 0; i < 10; i++) {
       int j = k - i; bool wrap = j < 0; if (wrap) j += 10;
       const uint32_t a = ((i & 1) && (j & 1)) ? f2[i] : f[i];
-      s = ed_mad(a, wrap ? g19[j] : g[j], s);
+      s = fd_mad(a, wrap ? g19[j] : g[j], s);
     }
     c[k] = s;
   }
@@ -31,11 +31,11 @@ __device__ __forceinline__ void mul255(uint32_t* r, const uint32_t* f, const uin
 }
 __global__ void k_mul29(uint32_t* o, const uint32_t* a, const uint32_t* b) {
   Fe x, y; for (int i = 0; i < 9; i++) { x.d[i] = a[threadIdx.x * 9 + i]; y.d[i] = b[threadIdx.x * 9 + i]; }
-  Fe r = fe_mul(x, y); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
+  Fe r = fd_mul(x, y); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
 }
 __global__ void k_sqr29(uint32_t* o, const uint32_t* a) {
   Fe x; for (int i = 0; i < 9; i++) x.d[i] = a[threadIdx.x * 9 + i];
-  Fe r = fe_sqr(x); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
+  Fe r = fd_sqr(x); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
 }
 __global__ void k_mul255(uint32_t* o, const uint32_t* a, const uint32_t* b) {
   uint32_t x[10], y[10], r[10]; for (int i = 0; i < 10; i++) { x[i] = a[threadIdx.x * 10 + i]; y[i] = b[threadIdx.x * 10 + i]; }

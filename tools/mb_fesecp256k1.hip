@@ -1,5 +1,5 @@
 // mb_fesecp256k1.hip -- ISA count of the two candidate forms of the field 2^256 - 2^32 - 977:
-// 9 x 29-bit digits with the 2^261 = 2^37 + 31264 fold (zg_ecdsa.h sf_mul / sf_sqr) against 8 x 32-bit
+// 9 x 29-bit digits with the 2^261 = 2^37 + 31264 fold (zg_fd9.h fd_mul / fd_sqr over Sf of zg_ecdsa.h) against 8 x 32-bit
 // saturated words with the 2^256 = 2^32 + 977 fold. Not run: compiled to assembly and counted.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 --offload-device-only -S -Izebra_amd/csrc -Iinclude
 //         -o mb_fesecp256k1.s tools/mb_fesecp256k1.hip, then count the instructions of each kernel
@@ -67,11 +67,11 @@ __device__ __forceinline__ void mul32(uint32_t* r, const uint32_t* a, const uint
 }
 __global__ void k_mul29(uint32_t* o, const uint32_t* a, const uint32_t* b) {
   Sf x, y; for (int i = 0; i < 9; i++) { x.d[i] = a[threadIdx.x * 9 + i]; y.d[i] = b[threadIdx.x * 9 + i]; }
-  Sf r = sf_mul(x, y); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
+  Sf r = fd_mul(x, y); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
 }
 __global__ void k_sqr29(uint32_t* o, const uint32_t* a) {
   Sf x; for (int i = 0; i < 9; i++) x.d[i] = a[threadIdx.x * 9 + i];
-  Sf r = sf_sqr(x); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
+  Sf r = fd_sqr(x); for (int i = 0; i < 9; i++) o[threadIdx.x * 9 + i] = r.d[i];
 }
 __global__ void k_mul32(uint32_t* o, const uint32_t* a, const uint32_t* b) {
   uint32_t x[8], y[8], r[8]; for (int i = 0; i < 8; i++) { x[i] = a[threadIdx.x * 8 + i]; y[i] = b[threadIdx.x * 8 + i]; }

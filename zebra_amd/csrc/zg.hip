@@ -19,6 +19,9 @@
 #include "../../include/zg.h"
 #include "zg_blake2b.h"
 #include "zg_chacha.h"
+#include "zg_ecdsa.h"    // ZG_EC_COMB_*
+#include "zg_ed25519.h"  // ZG_ED_COMB_*
+#include "zg_jubjub.h"   // ZG_JJ_COMB_*
 #include "zg_kernels.h"
 #include "zg_msm.h"
 #include "zg_prep.h"
@@ -1536,24 +1539,44 @@ extern "C" int zg_stats(zg_ctx* ctx, uint64_t* out, size_t n) {
   return ZG_OK;
 }
 
-// ------------------------------------------------------------------ Sapling signatures (zg_jubjub.h)
-#define ZG_JJ_COMB_BYTES (sizeof(uint32_t) * 16 * (size_t)(3 * 32 * 255))
-static int jj_comb(zg_ctx* ctx, const uint32_t** out) {
-  zg_dev* d = ctx->dev;
-  std::lock_guard<std::mutex> g(d->mu);
-  if (!d->jj_comb) {
+// ------------------------------------------------------------------ signature and header calls: shared pieces
+// a fixed-base comb table of the device (*slot, a member of zg_dev), built on first use by `launch`
+static int comb_table(zg_ctx* ctx, uint32_t** slot, size_t bytes, hipError_t (*launch)(hipStream_t, uint32_t*),
+                      const char* what, const uint32_t** out) {
+  std::lock_guard<std::mutex> g(ctx->dev->mu);
+  if (!*slot) {
     uint32_t* t = nullptr;
-    HIPCHK(hipMalloc(&t, ZG_JJ_COMB_BYTES));
-    hipError_t e = launch_jj_comb(ctx->stream, t);
+    HIPCHK(hipMalloc(&t, bytes));
+    hipError_t e = launch(ctx->stream, t);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
       hipFree(t);
-      return fail(ctx, ZG_E_HIP, std::string("Jubjub comb tables: ") + hipGetErrorString(e));
+      return fail(ctx, ZG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     }
-    d->jj_comb = t;
+    *slot = t;
   }
-  *out = d->jj_comb;
+  *out = *slot;
   return ZG_OK;
+}
+
+// The two events around a call's kernels (created on first use): sig_timed brackets the launch, sig_sync
+// waits for the stream after the copies back and keeps the kernel time for zg_last_sig_kernel_ms
+template <class Launch>
+static hipError_t sig_timed(zg_ctx* ctx, Launch launch) {
+  for (hipEvent_t& e : ctx->sig_ev)
+    if (!e) {
+      const hipError_t r = hipEventCreate(&e);
+      if (r != hipSuccess) return r;
+    }
+  hipError_t r = hipEventRecord(ctx->sig_ev[0], ctx->stream);
+  if (r == hipSuccess) r = launch();
+  if (r == hipSuccess) r = hipEventRecord(ctx->sig_ev[1], ctx->stream);
+  return r;
+}
+static hipError_t sig_sync(zg_ctx* ctx) {
+  const hipError_t r = hipStreamSynchronize(ctx->stream);
+  if (r == hipSuccess) hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  return r;
 }
 
 // device buffers of one call, freed on every path
@@ -1570,16 +1593,6 @@ struct DevScratch {
   }
 };
 
-// the two events around a signature call's kernel (created on first use)
-static hipError_t sig_events(zg_ctx* ctx) {
-  for (hipEvent_t& e : ctx->sig_ev)
-    if (!e) {
-      const hipError_t r = hipEventCreate(&e);
-      if (r != hipSuccess) return r;
-    }
-  return hipSuccess;
-}
-
 extern "C" int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms) {
   if (!ctx || !ms) return ZG_E_INVAL;
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -1587,6 +1600,7 @@ extern "C" int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms) {
   return ZG_OK;
 }
 
+// ------------------------------------------------------------------ Sapling signatures (zg_jubjub.h)
 extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                                    const uint8_t* gen, uint8_t* ok) {
   if (!ctx || (n && (!vk || !sig || !msg || !gen || !ok)) || n > (1u << 30)) return ZG_E_INVAL;
@@ -1594,7 +1608,8 @@ extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, con
   if (!n) return ZG_OK;
   HIPCHK(hipSetDevice(ctx->device));
   const uint32_t* comb = nullptr;
-  int rc = jj_comb(ctx, &comb);
+  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
+                      "Jubjub comb tables", &comb);
   if (rc) return rc;
   DevScratch s;
   uint8_t *dvk, *dsig, *dmsg, *dgen, *dok;
@@ -1607,36 +1622,13 @@ extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, con
   HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dmsg, msg, 64 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dgen, gen, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
-  HIPCHK(launch_redjubjub(ctx->stream, dvk, dsig, dmsg, dgen, (int)n, comb, dok));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] { return launch_redjubjub(ctx->stream, dvk, dsig, dmsg, dgen, (int)n, comb, dok); }));
   HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   return ZG_OK;
 }
 
 // ------------------------------------------------------------------ JoinSplit signatures (zg_ed25519.h)
-#define ZG_ED_COMB_BYTES (sizeof(uint32_t) * 27 * (size_t)(32 * 255))
-static int ed_comb(zg_ctx* ctx, const uint32_t** out) {
-  zg_dev* d = ctx->dev;
-  std::lock_guard<std::mutex> g(d->mu);
-  if (!d->ed_comb) {
-    uint32_t* t = nullptr;
-    HIPCHK(hipMalloc(&t, ZG_ED_COMB_BYTES));
-    hipError_t e = launch_ed_comb(ctx->stream, t);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      hipFree(t);
-      return fail(ctx, ZG_E_HIP, std::string("Ed25519 comb table: ") + hipGetErrorString(e));
-    }
-    d->ed_comb = t;
-  }
-  *out = d->ed_comb;
-  return ZG_OK;
-}
-
 extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
                                  uint8_t* status) {
   if (!ctx || (n && (!pubkey || !sig || !msg || !status)) || n > (1u << 30)) return ZG_E_INVAL;
@@ -1644,7 +1636,8 @@ extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, c
   if (!n) return ZG_OK;
   HIPCHK(hipSetDevice(ctx->device));
   const uint32_t* comb = nullptr;
-  int rc = ed_comb(ctx, &comb);
+  int rc = comb_table(ctx, &ctx->dev->ed_comb, sizeof(uint32_t) * ZG_ED_COMB_WORDS * ZG_ED_COMB_POINTS, launch_ed_comb,
+                      "Ed25519 comb table", &comb);
   if (rc) return rc;
   DevScratch s;
   uint8_t *dpk, *dsig, *dmsg, *dst;
@@ -1655,36 +1648,13 @@ extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, c
   HIPCHK(hipMemcpyAsync(dpk, pubkey, 32 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
-  HIPCHK(launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] { return launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst); }));
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   return ZG_OK;
 }
 
 // ------------------------------------------------------------------ transparent input signatures (zg_ecdsa.h)
-#define ZG_EC_COMB_BYTES (sizeof(uint32_t) * 18 * (size_t)(32 * 255))
-static int ec_comb(zg_ctx* ctx, const uint32_t** out) {
-  zg_dev* d = ctx->dev;
-  std::lock_guard<std::mutex> g(d->mu);
-  if (!d->ec_comb) {
-    uint32_t* t = nullptr;
-    HIPCHK(hipMalloc(&t, ZG_EC_COMB_BYTES));
-    hipError_t e = launch_ec_comb(ctx->stream, t);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      hipFree(t);
-      return fail(ctx, ZG_E_HIP, std::string("secp256k1 comb table: ") + hipGetErrorString(e));
-    }
-    d->ec_comb = t;
-  }
-  *out = d->ec_comb;
-  return ZG_OK;
-}
-
 extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* pubkey_len,
                                const uint8_t* sigs, const uint32_t* sig_off, const uint8_t* msg, uint8_t* status) {
   if (!ctx || (n && (!pubkeys || !pubkey_len || !sigs || !sig_off || !msg || !status)) || n > (1u << 30))
@@ -1695,7 +1665,8 @@ extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, co
   if (!n) return ZG_OK;
   HIPCHK(hipSetDevice(ctx->device));
   const uint32_t* comb = nullptr;
-  int rc = ec_comb(ctx, &comb);
+  int rc = comb_table(ctx, &ctx->dev->ec_comb, sizeof(uint32_t) * ZG_EC_COMB_WORDS * ZG_EC_COMB_POINTS, launch_ec_comb,
+                      "secp256k1 comb table", &comb);
   if (rc) return rc;
   const size_t sig_bytes = (size_t)sig_off[n] - sig_off[0];
   DevScratch s;
@@ -1712,14 +1683,10 @@ extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, co
   if (sig_bytes) HIPCHK(hipMemcpyAsync(dsig, sigs + sig_off[0], sig_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(doff, sig_off, sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
   // the device buffer starts at sig_off[0]: the kernel subtracts it
-  HIPCHK(launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, dmsg, (int)n, comb, dst));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] { return launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, dmsg, (int)n, comb, dst); }));
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   return ZG_OK;
 }
 
@@ -1823,15 +1790,14 @@ extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uin
     HIPCHK(hipMemcpyAsync(dout, out_off.data(), sizeof(uint32_t) * out_off.size(), hipMemcpyHostToDevice, ctx->stream));
   if (!jobs.empty())
     HIPCHK(hipMemcpyAsync(djobs, jobs.data(), sizeof(uint32_t) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
-  HIPCHK(launch_sighash_digests(ctx->stream, darena, dtxs, din, dout, djobs, (int)jobs.size(), ddig));
-  HIPCHK(launch_sighash_items(ctx->stream, darena, dtxs, din, dout, ddig, dscripts, ditems, (int)m, dhash));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] {
+    const hipError_t e = launch_sighash_digests(ctx->stream, darena, dtxs, din, dout, djobs, (int)jobs.size(), ddig);
+    if (e != hipSuccess) return e;
+    return launch_sighash_items(ctx->stream, darena, dtxs, din, dout, ddig, dscripts, ditems, (int)m, dhash);
+  }));
   std::vector<uint8_t> hh(32 * m);
   HIPCHK(hipMemcpyAsync(hh.data(), dhash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * sorted[k].slot, hh.data() + 32 * k, 32);
   return ZG_OK;
 }
@@ -1853,14 +1819,12 @@ extern "C" int zg_equihash_verify(zg_ctx* ctx, int params, size_t n, const uint8
   HIPCHK(s.alloc(&drep, n));
   HIPCHK(hipMemcpyAsync(din, inputs, input_len * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dsol, solutions, sb * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
-  HIPCHK(launch_equihash(ctx->stream, params, din, input_len, (int)input_len, dsol, sb, (int)n, dok, drep));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] {
+    return launch_equihash(ctx->stream, params, din, input_len, (int)input_len, dsol, sb, (int)n, dok, drep);
+  }));
   HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
   if (repeated) HIPCHK(hipMemcpyAsync(repeated, drep, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   return ZG_OK;
 }
 
@@ -1879,15 +1843,11 @@ extern "C" int zg_headers_verify(zg_ctx* ctx, size_t n, const uint8_t* headers, 
   HIPCHK(s.alloc(&dhash, 32 * n));
   HIPCHK(s.alloc(&dfl, n));
   HIPCHK(hipMemcpyAsync(dh, headers, (size_t)ZG_HEADER_BYTES * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_events(ctx));
-  HIPCHK(hipEventRecord(ctx->sig_ev[0], ctx->stream));
-  HIPCHK(launch_headers(ctx->stream, dh, (int)n, max_bits, dok, drep, dst, dhash, dfl));
-  HIPCHK(hipEventRecord(ctx->sig_ev[1], ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] { return launch_headers(ctx->stream, dh, (int)n, max_bits, dok, drep, dst, dhash, dfl); }));
   HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
   if (hashes) HIPCHK(hipMemcpyAsync(hashes, dhash, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
   if (flags) HIPCHK(hipMemcpyAsync(flags, dfl, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
+  HIPCHK(sig_sync(ctx));
   return ZG_OK;
 }
 
@@ -1906,7 +1866,8 @@ extern "C" int zg_sapling_bvk(zg_ctx* ctx, size_t ntx, const uint32_t* n_spends,
   if (off[ntx] && !cvs) return ZG_E_INVAL;
   HIPCHK(hipSetDevice(ctx->device));
   const uint32_t* comb = nullptr;
-  int rc = jj_comb(ctx, &comb);
+  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
+                      "Jubjub comb tables", &comb);
   if (rc) return rc;
   DevScratch s;
   uint32_t *doff, *dns;

@@ -19,8 +19,8 @@ namespace zg {
 
 // field: 0 Fq product (fq29_mul), 1 Fq square (fq29_sqr, b unused), 2 Fq2 product (f2_mul29,
 // a lazy < 2p per coefficient), 3 Fr product (fr29_mul), 4 BN254 Fq product (bq29_mul), 5 the product
-// mod 2^255 - 19 (fe_mul, canonical out), 6 (a + b 2^256) mod l (ed_mod_l), 7 the product mod the
-// secp256k1 field prime (sf_mul, canonical out), 8 the product mod the secp256k1 group order (sc_mul).
+// mod 2^255 - 19 (fd_mul over Fe, canonical out), 6 (a + b 2^256) mod l (ed_mod_l), 7 the product mod the
+// secp256k1 field prime (fd_mul over Sf, canonical out), 8 the product mod the secp256k1 group order (sc_mul).
 __global__ void k_debug_field(int field, int n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

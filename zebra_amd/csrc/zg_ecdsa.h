@@ -27,16 +27,8 @@
 //      a failure is ZG_ECDSA_SIGNATURE. normalize_s replaces s by n - s when s > n / 2: that negates
 //      R' and keeps x(R'), so the verdict does not depend on it and the kernel does not do it
 //
-// Field p = 2^256 - 2^32 - 977: 9 unsaturated digits of 29 bits, the layout of
-// zg_ed25519.h. A product is 81 carry-free v_mad_u64_u32 into 17 columns; the digit string is 261
-// bits long and 2^261 = 2^37 + 31264 (mod p) does not fit one 32-bit factor, so a high digit h of
-// column k folds as 31264 h into column k (one multiply-add) and h 2^8 into column k + 1 (a shift).
-// No digit is ever masked narrower than 29 bits and the small factors are hidden behind zg_opaque, so
-// no multiply-add sees two operands it knows to fit 24 bits (DESIGN.md section 4;
-// zg_debug_field_mul field 7 is the guard).
-//   "tight" element: every digit < 2^29 + 2^21 (what every function here returns);
-//   products accept digits < 1.4e9 (9 x^2 + the folds stay below 2^64), i.e. also an uncarried sum
-//   of two tight elements (sf_add_nc); sf_sub and sf_mul21 take tight operands only.
+// Field p = 2^256 - 2^32 - 977: the 9 x 29-bit digit field of zg_fd9.h (the fold is 2^261 = 2^37 +
+// 31264); sf_mul21 here takes a tight operand only.
 // Scalars mod n = 2^256 - c, c < 2^129: 8 saturated 32-bit words, any value below 2^256 in, the
 // canonical value out. A 512-bit product is folded three times with 2^256 = c (mod n), every carry
 // kept (n leaves no headroom in 256 bits: the generic Fp<M> add would drop the carry). One Fermat
@@ -45,7 +37,7 @@
 // Renes-Costello-Batina 2016 for a = 0 (algorithms 7 and 9, b3 = 21): secp256k1 has prime order, so
 // they are correct for every pair of inputs -- P + P, P + (-P), infinity as an operand or the result.
 #pragma once
-#include "zg_field.h"
+#include "zg_fd9.h"
 
 namespace zg {
 
@@ -54,10 +46,11 @@ namespace zg {
 #define ZG_EC_COMB_WORDS 18  // x, y: 9 digits each
 #define ZG_EC_COMB_POINTS (ZG_EC_COMB_W * ZG_EC_COMB_D)
 
-struct Sf {
-  uint32_t d[9];
+struct EcFM {  // 2^256 - 2^32 - 977
+  static constexpr int BITS = 256, C1SH = 32;
+  static constexpr uint32_t C0 = 977;
 };
-static constexpr uint32_t SF_MASK = 0x1fffffffu;
+using Sf = Fd9<EcFM>;
 static constexpr uint32_t EC_P[8] = {0xfffffc2fu, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 static constexpr uint32_t EC_N[8] = {0xd0364141u, 0xbfd25e8cu, 0xaf48a03bu, 0xbaaedce6u, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 static constexpr uint32_t EC_NM2[8] = {0xd036413fu, 0xbfd25e8cu, 0xaf48a03bu, 0xbaaedce6u, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // n - 2
@@ -66,54 +59,6 @@ static constexpr uint32_t EC_PMN[8] = {0x2fc9baeeu, 0x402da172u, 0x50b75fc4u, 0x
 static constexpr uint32_t EC_GX[8] = {0x16f81798u, 0x59f2815bu, 0x2dce28d9u, 0x029bfcdbu, 0xce870b07u, 0x55a06295u, 0xf9dcbbacu, 0x79be667eu};
 static constexpr uint32_t EC_GY[8] = {0xfb10d4b8u, 0x9c47d08fu, 0xa6855419u, 0xfd17b448u, 0x0e1108a8u, 0x5da4fbfcu, 0x26a3c465u, 0x483ada77u};
 
-ZG_INL uint64_t sf_mad(uint32_t a, uint32_t b, uint64_t c) { return (uint64_t)a * b + c; }
-
-ZG_INL Sf sf_zero() {
-  Sf r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.d[i] = 0;
-  return r;
-}
-ZG_INL Sf sf_small(uint32_t v) {  // v < 2^29
-  Sf r = sf_zero();
-  r.d[0] = v;
-  return r;
-}
-
-// one carry pass with the 2^261 = 2^37 + 31264 fold: digits < 2^31 in -> tight out (the value is unchanged mod p)
-ZG_INL void sf_carry(Sf& r) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    r.d[k + 1] += r.d[k] >> 29;
-    r.d[k] &= SF_MASK;
-  }
-  const uint32_t t = r.d[8] >> 29;
-  r.d[8] &= SF_MASK;
-  r.d[0] += t * 31264u;
-  r.d[1] += t << 8;
-}
-ZG_INL Sf sf_add_nc(const Sf& a, const Sf& b) {  // a product operand only
-  Sf r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.d[i] = a.d[i] + b.d[i];
-  return r;
-}
-ZG_INL Sf sf_add(const Sf& a, const Sf& b) {
-  Sf r = sf_add_nc(a, b);
-  sf_carry(r);
-  return r;
-}
-// a - b: a + 2 (2^261 - 2^37 - 31264) - b digit by digit (every digit of the offset >= a tight digit)
-ZG_INL Sf sf_sub(const Sf& a, const Sf& b) {
-  Sf r;
-  r.d[0] = a.d[0] + (0x40000000u - 62528u) - b.d[0];
-  r.d[1] = a.d[1] + (0x40000000u - 514u) - b.d[1];
-#pragma unroll
-  for (int i = 2; i < 9; i++) r.d[i] = a.d[i] + 0x3ffffffeu - b.d[i];
-  sf_carry(r);
-  return r;
-}
-ZG_INL Sf sf_neg(const Sf& a) { return sf_sub(sf_zero(), a); }
 // 21 a (b3 = 3 * 7 of the point formulas), a tight
 ZG_INL Sf sf_mul21(const Sf& a) {
   uint32_t f = 21u;
@@ -122,181 +67,40 @@ ZG_INL Sf sf_mul21(const Sf& a) {
   uint64_t c = 0;
 #pragma unroll
   for (int k = 0; k < 9; k++) {
-    c = sf_mad(a.d[k], f, c);
-    r.d[k] = (uint32_t)c & SF_MASK;
+    c = fd_mad(a.d[k], f, c);
+    r.d[k] = (uint32_t)c & Sf::MASK;
     c >>= 29;
   }
-  const uint32_t t = (uint32_t)c;  // < 32
-  r.d[0] += t * 31264u;
-  r.d[1] += t << 8;
+  r.fold_in((uint32_t)c);  // < 32
   return r;
-}
-
-// 17 columns (each < 2^64 - 2^59) -> tight element
-ZG_INL Sf sf_fold(uint64_t* c) {
-  uint32_t h[9];
-#pragma unroll
-  for (int k = 9; k < 16; k++) {
-    h[k - 9] = (uint32_t)c[k] & SF_MASK;
-    c[k + 1] += c[k] >> 29;
-  }
-  h[7] = (uint32_t)c[16] & SF_MASK;
-  h[8] = (uint32_t)(c[16] >> 29);  // < 2^32 by the operand bound
-  uint32_t f = 31264u;
-  zg_opaque(f);
-#pragma unroll
-  for (int k = 0; k < 9; k++) c[k] = sf_mad(h[k], f, c[k]);
-#pragma unroll
-  for (int k = 0; k < 8; k++) c[k + 1] += (uint64_t)h[k] << 8;
-  uint64_t c9 = (uint64_t)h[8] << 8;
-  Sf r;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    r.d[k] = (uint32_t)c[k] & SF_MASK;
-    c[k + 1] += c[k] >> 29;
-  }
-  r.d[8] = (uint32_t)c[8] & SF_MASK;
-  c9 += c[8] >> 29;  // < 2^41: folds into digits 0, 1 and 2
-  uint32_t tl = (uint32_t)c9 & SF_MASK, th = (uint32_t)(c9 >> 29);
-  zg_opaque(th);
-  const uint64_t c0 = sf_mad(tl, f, r.d[0]);
-  const uint64_t c1 = sf_mad(th, f, (uint64_t)r.d[1] + ((uint64_t)tl << 8) + (c0 >> 29));
-  r.d[0] = (uint32_t)c0 & SF_MASK;
-  r.d[1] = (uint32_t)c1 & SF_MASK;
-  r.d[2] += (uint32_t)(c1 >> 29) + (th << 8);
-  return r;
-}
-
-ZG_INL Sf sf_mul(const Sf& a, const Sf& b) {
-  uint64_t c[17];
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    uint64_t s = 0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (j < 0 || j > 8) continue;
-      s = sf_mad(a.d[i], b.d[j], s);
-    }
-    c[k] = s;
-  }
-  return sf_fold(c);
-}
-ZG_INL Sf sf_sqr(const Sf& a) {
-  uint32_t a2[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) a2[i] = a.d[i] << 1;
-  uint64_t c[17];
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    uint64_t s = 0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (j < 0 || j > 8 || i > j) continue;
-      s = sf_mad(i < j ? a2[i] : a.d[i], a.d[j], s);
-    }
-    c[k] = s;
-  }
-  return sf_fold(c);
-}
-ZG_INL Sf sf_sqr_n(Sf a, int n) {
-  for (int i = 0; i < n; i++) a = sf_sqr(a);
-  return a;
-}
-
-// a 256-bit integer (8 LE words, any value) -> digits (tight: the top digit has 24 bits)
-ZG_INL Sf sf_from_words(const uint32_t* w) {
-  Sf r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const int bit = 29 * k, wi = bit >> 5, sh = bit & 31;
-    uint32_t v = w[wi] >> sh;
-    if (sh > 3 && wi + 1 < 8) v |= w[wi + 1] << (32 - sh);
-    r.d[k] = v & SF_MASK;
-  }
-  return r;
-}
-// the canonical value (< p) as 8 LE words
-ZG_INL void sf_canon(const Sf& a, uint32_t* w) {
-  Sf t = a;
-  sf_carry(t);
-  sf_carry(t);  // every digit < 2^29: the value is < 2^261
-  const uint32_t q = t.d[8] >> 24;
-  t.d[8] &= 0xffffffu;
-  t.d[0] += 977u * q;  // 2^256 = 2^32 + 977
-  t.d[1] += q << 3;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    t.d[k + 1] += t.d[k] >> 29;
-    t.d[k] &= SF_MASK;
-  }
-  // t < 2^256 + 2^38: t >= p iff t + 2^32 + 977 reaches bit 256
-  Sf u = t;
-  u.d[0] += 977u;
-  u.d[1] += 8u;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    u.d[k + 1] += u.d[k] >> 29;
-    u.d[k] &= SF_MASK;
-  }
-  const bool ge = (u.d[8] >> 24) != 0;
-  u.d[8] &= 0xffffffu;
-  uint64_t acc = 0;
-  int bits = 0, wi = 0;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    acc |= (uint64_t)(ge ? u.d[k] : t.d[k]) << bits;
-    bits += 29;
-    if (bits >= 32) {
-      w[wi++] = (uint32_t)acc;
-      acc >>= 32;
-      bits -= 32;
-    }
-  }
-}
-ZG_INL bool sf_eq(const Sf& a, const Sf& b) {
-  uint32_t x[8], y[8], acc = 0;
-  sf_canon(a, x);
-  sf_canon(b, y);
-#pragma unroll
-  for (int i = 0; i < 8; i++) acc |= x[i] ^ y[i];
-  return acc == 0;
-}
-ZG_INL bool sf_is_zero(const Sf& a) {
-  uint32_t x[8], acc = 0;
-  sf_canon(a, x);
-#pragma unroll
-  for (int i = 0; i < 8; i++) acc |= x[i];
-  return acc == 0;
 }
 
 // z^(2^223 - 1) 2^23 z^(2^22 - 1), the common head of the square root and the inverse; *x2 = z^3
 ZG_INL Sf sf_pow_head(const Sf& z, Sf* x2) {
-  *x2 = sf_mul(sf_sqr(z), z);
-  const Sf x3 = sf_mul(sf_sqr(*x2), z);
-  const Sf x6 = sf_mul(sf_sqr_n(x3, 3), x3);
-  const Sf x9 = sf_mul(sf_sqr_n(x6, 3), x3);
-  const Sf x11 = sf_mul(sf_sqr_n(x9, 2), *x2);
-  const Sf x22 = sf_mul(sf_sqr_n(x11, 11), x11);
-  const Sf x44 = sf_mul(sf_sqr_n(x22, 22), x22);
-  const Sf x88 = sf_mul(sf_sqr_n(x44, 44), x44);
-  const Sf x176 = sf_mul(sf_sqr_n(x88, 88), x88);
-  const Sf x220 = sf_mul(sf_sqr_n(x176, 44), x44);
-  const Sf x223 = sf_mul(sf_sqr_n(x220, 3), x3);
-  return sf_mul(sf_sqr_n(x223, 23), x22);
+  *x2 = fd_mul(fd_sqr(z), z);
+  const Sf x3 = fd_mul(fd_sqr(*x2), z);
+  const Sf x6 = fd_mul(fd_sqr_n(x3, 3), x3);
+  const Sf x9 = fd_mul(fd_sqr_n(x6, 3), x3);
+  const Sf x11 = fd_mul(fd_sqr_n(x9, 2), *x2);
+  const Sf x22 = fd_mul(fd_sqr_n(x11, 11), x11);
+  const Sf x44 = fd_mul(fd_sqr_n(x22, 22), x22);
+  const Sf x88 = fd_mul(fd_sqr_n(x44, 44), x44);
+  const Sf x176 = fd_mul(fd_sqr_n(x88, 88), x88);
+  const Sf x220 = fd_mul(fd_sqr_n(x176, 44), x44);
+  const Sf x223 = fd_mul(fd_sqr_n(x220, 3), x3);
+  return fd_mul(fd_sqr_n(x223, 23), x22);
 }
 ZG_INL Sf sf_inv(const Sf& z) {  // z^(p - 2)
   Sf x2;
   Sf t = sf_pow_head(z, &x2);
-  t = sf_mul(sf_sqr_n(t, 5), z);
-  t = sf_mul(sf_sqr_n(t, 3), x2);
-  return sf_mul(sf_sqr_n(t, 2), z);
+  t = fd_mul(fd_sqr_n(t, 5), z);
+  t = fd_mul(fd_sqr_n(t, 3), x2);
+  return fd_mul(fd_sqr_n(t, 2), z);
 }
 ZG_INL Sf sf_sqrt_candidate(const Sf& z) {  // z^((p + 1) / 4): a root iff z is a square
   Sf x2;
   const Sf t = sf_pow_head(z, &x2);
-  return sf_sqr_n(sf_mul(sf_sqr_n(t, 6), x2), 2);
+  return fd_sqr_n(fd_mul(fd_sqr_n(t, 6), x2), 2);
 }
 
 // ---- 256-bit words
@@ -335,7 +139,7 @@ ZG_INL void sc_mp_mul(uint32_t* r, const uint32_t* a, const uint32_t* b) {
     uint64_t carry = 0;
 #pragma unroll
     for (int j = 0; j < NB; j++) {
-      const uint64_t t = sf_mad(a[i], b[j], (uint64_t)r[i + j] + carry);
+      const uint64_t t = fd_mad(a[i], b[j], (uint64_t)r[i + j] + carry);
       r[i + j] = (uint32_t)t;
       carry = t >> 32;
     }
@@ -348,7 +152,7 @@ ZG_INL uint32_t sc_add_kc(uint32_t* z, uint32_t k, const uint32_t* c) {
   uint64_t carry = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    const uint64_t t = i < 5 ? sf_mad(k, c[i], (uint64_t)z[i] + carry) : (uint64_t)z[i] + carry;
+    const uint64_t t = i < 5 ? fd_mad(k, c[i], (uint64_t)z[i] + carry) : (uint64_t)z[i] + carry;
     z[i] = (uint32_t)t;
     carry = t >> 32;
   }
@@ -421,39 +225,39 @@ ZG_INL void sc_inv(uint32_t* r, const uint32_t* a) {
 struct EcP {
   Sf X, Y, Z;  // x = X / Z, y = Y / Z; infinity = (0 : 1 : 0)
 };
-ZG_INL EcP ec_infinity() { return {sf_zero(), sf_small(1), sf_zero()}; }
+ZG_INL EcP ec_infinity() { return {Sf::zero(), Sf::small(1), Sf::zero()}; }
 // Renes-Costello-Batina algorithm 7 (a = 0): complete
 ZG_INL EcP ec_add(const EcP& p, const EcP& q) {
-  Sf t0 = sf_mul(p.X, q.X), t1 = sf_mul(p.Y, q.Y), t2 = sf_mul(p.Z, q.Z);
-  const Sf t3 = sf_sub(sf_mul(sf_add_nc(p.X, p.Y), sf_add_nc(q.X, q.Y)), sf_add(t0, t1));  // X1 Y2 + X2 Y1
-  const Sf t4 = sf_sub(sf_mul(sf_add_nc(p.Y, p.Z), sf_add_nc(q.Y, q.Z)), sf_add(t1, t2));  // Y1 Z2 + Y2 Z1
-  Sf y3 = sf_sub(sf_mul(sf_add_nc(p.X, p.Z), sf_add_nc(q.X, q.Z)), sf_add(t0, t2));        // X1 Z2 + X2 Z1
-  t0 = sf_add(sf_add(t0, t0), t0);
+  Sf t0 = fd_mul(p.X, q.X), t1 = fd_mul(p.Y, q.Y), t2 = fd_mul(p.Z, q.Z);
+  const Sf t3 = fd_sub(fd_mul(fd_add_nc(p.X, p.Y), fd_add_nc(q.X, q.Y)), fd_add(t0, t1));  // X1 Y2 + X2 Y1
+  const Sf t4 = fd_sub(fd_mul(fd_add_nc(p.Y, p.Z), fd_add_nc(q.Y, q.Z)), fd_add(t1, t2));  // Y1 Z2 + Y2 Z1
+  Sf y3 = fd_sub(fd_mul(fd_add_nc(p.X, p.Z), fd_add_nc(q.X, q.Z)), fd_add(t0, t2));        // X1 Z2 + X2 Z1
+  t0 = fd_add(fd_add(t0, t0), t0);
   t2 = sf_mul21(t2);
-  Sf z3 = sf_add(t1, t2);
-  t1 = sf_sub(t1, t2);
+  Sf z3 = fd_add(t1, t2);
+  t1 = fd_sub(t1, t2);
   y3 = sf_mul21(y3);
-  const Sf x3 = sf_sub(sf_mul(t3, t1), sf_mul(t4, y3));
-  y3 = sf_add(sf_mul(y3, t0), sf_mul(t1, z3));
-  z3 = sf_add(sf_mul(z3, t4), sf_mul(t0, t3));
+  const Sf x3 = fd_sub(fd_mul(t3, t1), fd_mul(t4, y3));
+  y3 = fd_add(fd_mul(y3, t0), fd_mul(t1, z3));
+  z3 = fd_add(fd_mul(z3, t4), fd_mul(t0, t3));
   return {x3, y3, z3};
 }
 // algorithm 9 (a = 0): complete
 ZG_INL EcP ec_dbl(const EcP& p) {
-  Sf t0 = sf_sqr(p.Y);
-  Sf z3 = sf_add(t0, t0);
-  z3 = sf_add(z3, z3);
-  z3 = sf_add(z3, z3);
-  const Sf t1 = sf_mul(p.Y, p.Z);
-  Sf t2 = sf_mul21(sf_sqr(p.Z));
-  const Sf x3 = sf_mul(t2, z3);
-  Sf y3 = sf_add(t0, t2);
-  z3 = sf_mul(t1, z3);
-  t2 = sf_add(sf_add(t2, t2), t2);
-  t0 = sf_sub(t0, t2);
-  y3 = sf_add(sf_mul(t0, y3), x3);
-  const Sf xy = sf_mul(t0, sf_mul(p.X, p.Y));
-  return {sf_add(xy, xy), y3, z3};
+  Sf t0 = fd_sqr(p.Y);
+  Sf z3 = fd_add(t0, t0);
+  z3 = fd_add(z3, z3);
+  z3 = fd_add(z3, z3);
+  const Sf t1 = fd_mul(p.Y, p.Z);
+  Sf t2 = sf_mul21(fd_sqr(p.Z));
+  const Sf x3 = fd_mul(t2, z3);
+  Sf y3 = fd_add(t0, t2);
+  z3 = fd_mul(t1, z3);
+  t2 = fd_add(fd_add(t2, t2), t2);
+  t0 = fd_sub(t0, t2);
+  y3 = fd_add(fd_mul(t0, y3), x3);
+  const Sf xy = fd_mul(t0, fd_mul(p.X, p.Y));
+  return {fd_add(xy, xy), y3, z3};
 }
 // [k] p for the low nbits of k (8 LE words), the scalar in a shift register
 ZG_INL EcP ec_mul(const EcP& p, const uint32_t* k, int nbits) {
@@ -493,7 +297,7 @@ ZG_INL EcP ec_add_fixed(EcP acc, const uint32_t* comb, const uint32_t* s) {
       q.X.d[l] = t[l];
       q.Y.d[l] = t[9 + l];
     }
-    q.Z = sf_small(1);
+    q.Z = Sf::small(1);
     acc = ec_add(acc, q);
   }
   return acc;
@@ -510,24 +314,24 @@ ZG_INL bool ec_parse_pubkey(const uint8_t* pk, int len, EcP* out) {
   for (int i = 0; i < 8; i++) p[i] = EC_P[i];
   ec_load_be(pk + 1, xw);
   if (!ec_words_lt(xw, p)) return false;
-  const Sf x = sf_from_words(xw);
-  const Sf rhs = sf_add(sf_mul(sf_sqr(x), x), sf_small(7));
+  const Sf x = Sf::from_words(xw);
+  const Sf rhs = fd_add(fd_mul(fd_sqr(x), x), Sf::small(7));
   Sf y;
   if (len == 33) {
     y = sf_sqrt_candidate(rhs);
-    if (!sf_eq(sf_sqr(y), rhs)) return false;
+    if (!fd_eq(fd_sqr(y), rhs)) return false;
     uint32_t yc[8];
-    sf_canon(y, yc);
-    if ((yc[0] & 1u) != (pre & 1u)) y = sf_neg(y);
+    fd_canon(y, yc);
+    if ((yc[0] & 1u) != (pre & 1u)) y = fd_neg(y);
   } else {
     uint32_t yw[8];
     ec_load_be(pk + 33, yw);
     if (!ec_words_lt(yw, p)) return false;
     if (pre != 4 && (yw[0] & 1u) != (pre & 1u)) return false;
-    y = sf_from_words(yw);
-    if (!sf_eq(sf_sqr(y), rhs)) return false;
+    y = Sf::from_words(yw);
+    if (!fd_eq(fd_sqr(y), rhs)) return false;
   }
-  *out = {x, y, sf_small(1)};
+  *out = {x, y, Sf::small(1)};
   return true;
 }
 
@@ -618,9 +422,9 @@ ZG_INL uint8_t ecdsa_verify_one(const uint8_t* pubkey, int pubkey_len, const uin
   sc_mul(u2, r, si);
   EcP R = ec_mul(Q, u2, 256);
   R = ec_add_fixed(R, comb, u1);
-  if (sf_is_zero(R.Z)) return 3;
+  if (fd_is_zero(R.Z)) return 3;
   // x(R') = X / Z: compare X with r Z, and with (r + n) Z when r + n < p
-  if (sf_eq(R.X, sf_mul(sf_from_words(r), R.Z))) return 0;
+  if (fd_eq(R.X, fd_mul(Sf::from_words(r), R.Z))) return 0;
   uint32_t pmn[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) pmn[i] = EC_PMN[i];
@@ -632,7 +436,7 @@ ZG_INL uint8_t ecdsa_verify_one(const uint8_t* pubkey, int pubkey_len, const uin
     r[i] = (uint32_t)t;
     carry = t >> 32;
   }
-  return sf_eq(R.X, sf_mul(sf_from_words(r), R.Z)) ? 0 : 3;
+  return fd_eq(R.X, fd_mul(Sf::from_words(r), R.Z)) ? 0 : 3;
 }
 
 // comb table entry t: (d + 1) 2^(8 w) G as affine (x, y), canonical digits
@@ -644,17 +448,17 @@ ZG_INL void ec_comb_entry(int t, uint32_t* e) {
   uint32_t g[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) g[i] = EC_GX[i];
-  const Sf gx = sf_from_words(g);
+  const Sf gx = Sf::from_words(g);
 #pragma unroll
   for (int i = 0; i < 8; i++) g[i] = EC_GY[i];
-  const Sf gy = sf_from_words(g);
-  const EcP p = ec_mul({gx, gy, sf_small(1)}, k, 8 * w + 8);
+  const Sf gy = Sf::from_words(g);
+  const EcP p = ec_mul({gx, gy, Sf::small(1)}, k, 8 * w + 8);
   const Sf zi = sf_inv(p.Z);
   uint32_t c[8];
-  sf_canon(sf_mul(p.X, zi), c);
-  const Sf x = sf_from_words(c);
-  sf_canon(sf_mul(p.Y, zi), c);
-  const Sf y = sf_from_words(c);
+  fd_canon(fd_mul(p.X, zi), c);
+  const Sf x = Sf::from_words(c);
+  fd_canon(fd_mul(p.Y, zi), c);
+  const Sf y = Sf::from_words(c);
   for (int l = 0; l < 9; l++) {
     e[l] = x.d[l];
     e[9 + l] = y.d[l];
@@ -663,7 +467,7 @@ ZG_INL void ec_comb_entry(int t, uint32_t* e) {
 
 // debug entries (zg_debug_field_mul fields 7 and 8), 8-word operands of any value and canonical result
 ZG_INL void ec_debug_sf_mul(uint32_t* r, const uint32_t* a, const uint32_t* b) {
-  sf_canon(sf_mul(sf_from_words(a), sf_from_words(b)), r);
+  fd_canon(fd_mul(Sf::from_words(a), Sf::from_words(b)), r);
 }
 ZG_INL void ec_debug_sc_mul(uint32_t* r, const uint32_t* a, const uint32_t* b) { sc_mul(r, a, b); }
 

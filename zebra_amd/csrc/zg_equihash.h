@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "zg_hash.h"  // blake2b_init, blake2b_compress, sha256_compress
+
 #define ZG_HD __host__ __device__
 
 namespace zg {
@@ -68,80 +70,5 @@ ZG_HD inline bool pow_valid_words(uint32_t max_bits, uint32_t bits, const uint32
   if (!compact_to_u256(bits, target)) return false;
   return u256_le(target, maximum) && u256_le(hash, target);
 }
-
-#ifdef __HIPCC__
-// ---- BLAKE2b (RFC 7693) compression on one lane, 64-bit words in plain C++. The rotation by 32 is a
-// renaming of the register pair; those by 24, 16 and 63 are written over the two halves with the
-// 32-bit funnel shift (v_alignbit_b32, one per half): left as (x >> k) | (x << (64 - k)) the compiler
-// emits a 64-bit shift, a 32-bit shift and an or per rotation.
-template <int K>
-ZG_HD __forceinline__ uint64_t b2_rotr(uint64_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-  if (K == 32) return ((uint64_t)lo << 32) | hi;
-  if (K < 32)
-    return ((uint64_t)__builtin_amdgcn_alignbit(lo, hi, K) << 32) | __builtin_amdgcn_alignbit(hi, lo, K);
-  return ((uint64_t)__builtin_amdgcn_alignbit(hi, lo, K - 32) << 32) | __builtin_amdgcn_alignbit(lo, hi, K - 32);
-#else
-  return (x >> K) | (x << (64 - K));
-#endif
-}
-
-ZG_HD __forceinline__ void blake2b_init(uint64_t h[8], uint32_t outlen, uint64_t person0, uint64_t person1) {
-  const uint64_t iv[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
-                          0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] = iv[i];
-  h[0] ^= 0x01010000ull ^ (uint64_t)outlen;
-  h[6] ^= person0;  // parameter block bytes 48..63
-  h[7] ^= person1;
-}
-
-#define ZG_B2_G(a, b, c, d, x, y) \
-  do {                            \
-    v[a] = v[a] + v[b] + (x);     \
-    v[d] = b2_rotr<32>(v[d] ^ v[a]); \
-    v[c] = v[c] + v[d];           \
-    v[b] = b2_rotr<24>(v[b] ^ v[c]); \
-    v[a] = v[a] + v[b] + (y);     \
-    v[d] = b2_rotr<16>(v[d] ^ v[a]); \
-    v[c] = v[c] + v[d];           \
-    v[b] = b2_rotr<63>(v[b] ^ v[c]); \
-  } while (0)
-
-// h <- F(h, m, t, last); t < 2^64 (the high counter word is zero)
-ZG_HD __forceinline__ void blake2b_compress(uint64_t h[8], const uint64_t m[16], uint64_t t, bool last) {
-  constexpr uint8_t S[12][16] = {
-      {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
-      {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
-      {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
-      {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
-      {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
-      {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
-  const uint64_t iv[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
-                          0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
-  uint64_t v[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    v[i] = h[i];
-    v[i + 8] = iv[i];
-  }
-  v[12] ^= t;
-  if (last) v[14] = ~v[14];
-#pragma unroll
-  for (int r = 0; r < 12; r++) {
-    ZG_B2_G(0, 4, 8, 12, m[S[r][0]], m[S[r][1]]);
-    ZG_B2_G(1, 5, 9, 13, m[S[r][2]], m[S[r][3]]);
-    ZG_B2_G(2, 6, 10, 14, m[S[r][4]], m[S[r][5]]);
-    ZG_B2_G(3, 7, 11, 15, m[S[r][6]], m[S[r][7]]);
-    ZG_B2_G(0, 5, 10, 15, m[S[r][8]], m[S[r][9]]);
-    ZG_B2_G(1, 6, 11, 12, m[S[r][10]], m[S[r][11]]);
-    ZG_B2_G(2, 7, 8, 13, m[S[r][12]], m[S[r][13]]);
-    ZG_B2_G(3, 4, 9, 14, m[S[r][14]], m[S[r][15]]);
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
-}
-#endif  // __HIPCC__
 
 }  // namespace zg

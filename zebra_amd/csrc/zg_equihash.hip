@@ -7,7 +7,6 @@
 
 #include "../../include/zg.h"
 #include "zg_equihash.h"
-#include "zg_merkle.h"  // ZG_SHA256_K, sha_rotr, sha256_compress_words
 
 namespace zg {
 
@@ -200,29 +199,6 @@ hipError_t launch_equihash(hipStream_t st, int params, const uint8_t* inputs, si
   return hipErrorInvalidValue;
 }
 
-// ---- SHA-256 over a message longer than one block: one compression chained on st (FIPS 180-4 6.2.2);
-// w: the 16 message words, big-endian values
-__device__ __forceinline__ void sha256_block(uint32_t st[8], uint32_t w[16]) {
-  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-  for (int t = 0; t < 64; t++) {
-    uint32_t wt;
-    if (t < 16) {
-      wt = w[t];
-    } else {
-      const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-      const uint32_t s0 = sha_rotr(w15, 7) ^ sha_rotr(w15, 18) ^ (w15 >> 3);
-      const uint32_t s1 = sha_rotr(w2, 17) ^ sha_rotr(w2, 19) ^ (w2 >> 10);
-      wt = w[t & 15] = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-    }
-    const uint32_t t1 = h + (sha_rotr(e, 6) ^ sha_rotr(e, 11) ^ sha_rotr(e, 25)) + ((e & f) ^ (~e & g)) +
-                        ZG_SHA256_K[t] + wt;
-    const uint32_t t2 = (sha_rotr(a, 2) ^ sha_rotr(a, 13) ^ sha_rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-    h = g, g = f, f = e, e = d + t1, d = c, c = b, b = a, a = t1 + t2;
-  }
-  st[0] += a, st[1] += b, st[2] += c, st[3] += d, st[4] += e, st[5] += f, st[6] += g, st[7] += h;
-}
-
 // eq_ok / eq_rep: the verdicts of k_equihash<200, 9> over the same headers (same stream, launched before)
 __global__ void __launch_bounds__(64)
 k_header_pow(const uint8_t* __restrict__ headers, int n, uint32_t max_bits, const uint8_t* __restrict__ eq_ok,
@@ -249,7 +225,7 @@ k_header_pow(const uint8_t* __restrict__ headers, int n, uint32_t max_bits, cons
       w[k] = x;
     }
     if (b == BLOCKS - 1) w[15] = 8u * ZG_HEADER_BYTES;
-    sha256_block(st, w);
+    sha256_compress(st, w);
   }
   // SHA-256 of those 32 bytes: one block from the IV
   uint32_t lw[8], rw[8], hash[8];

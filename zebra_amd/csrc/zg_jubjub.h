@@ -19,6 +19,7 @@
 // [S] P_G uses fixed-base comb tables of the generators (8-bit digits, 32 mixed additions);
 // [c] vk is a 252-bit double-and-add.
 #pragma once
+#include "zg_hash.h"
 #include "zg_prep.h"
 
 namespace zg {
@@ -130,55 +131,10 @@ ZG_INL JExt jj_fixed_mul(const uint32_t* comb, int gen, const uint32_t* s) {
 }
 
 // ---- BLAKE2b-512 of at most 128 bytes with a 16-byte personalization (one compression)
-__device__ __constant__ const uint8_t JJ_SIGMA[12][16] = {
-    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
-    {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
-    {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
-    {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
-    {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
-    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
-__device__ __constant__ const uint64_t JJ_IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull,
-                                                  0xa54ff53a5f1d36f1ull, 0x510e527fade682d1ull, 0x9b05688c2b3e6c1full,
-                                                  0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
-__device__ inline uint64_t jj_rotr(uint64_t x, int k) { return (x >> k) | (x << (64 - k)); }
 // m: the message block as 16 LE words (zero-padded), len bytes of it; out: 8 LE words
 __device__ inline void blake2b512_block(const uint64_t* m, int len, const char* personal, uint64_t* out) {
-  uint64_t h[8], v[16];
-  for (int i = 0; i < 8; i++) h[i] = JJ_IV[i];
-  h[0] ^= 0x01010000ull ^ 64ull;
-  for (int w = 0; w < 2; w++) {
-    uint64_t p = 0;
-    for (int b = 7; b >= 0; b--) p = (p << 8) | (uint8_t)personal[8 * w + b];
-    h[6 + w] ^= p;
-  }
-  for (int i = 0; i < 8; i++) {
-    v[i] = h[i];
-    v[i + 8] = JJ_IV[i];
-  }
-  v[12] ^= (uint64_t)len;
-  v[14] = ~v[14];
-  for (int r = 0; r < 12; r++) {
-    const uint8_t* s = JJ_SIGMA[r];
-#define JJ_G(a, b, c, d, x, y)           \
-  v[a] = v[a] + v[b] + (x);              \
-  v[d] = jj_rotr(v[d] ^ v[a], 32);       \
-  v[c] = v[c] + v[d];                    \
-  v[b] = jj_rotr(v[b] ^ v[c], 24);       \
-  v[a] = v[a] + v[b] + (y);              \
-  v[d] = jj_rotr(v[d] ^ v[a], 16);       \
-  v[c] = v[c] + v[d];                    \
-  v[b] = jj_rotr(v[b] ^ v[c], 63);
-    JJ_G(0, 4, 8, 12, m[s[0]], m[s[1]]);
-    JJ_G(1, 5, 9, 13, m[s[2]], m[s[3]]);
-    JJ_G(2, 6, 10, 14, m[s[4]], m[s[5]]);
-    JJ_G(3, 7, 11, 15, m[s[6]], m[s[7]]);
-    JJ_G(0, 5, 10, 15, m[s[8]], m[s[9]]);
-    JJ_G(1, 6, 11, 12, m[s[10]], m[s[11]]);
-    JJ_G(2, 7, 8, 13, m[s[12]], m[s[13]]);
-    JJ_G(3, 4, 9, 14, m[s[14]], m[s[15]]);
-#undef JJ_G
-  }
-  for (int i = 0; i < 8; i++) out[i] = h[i] ^ v[i] ^ v[i + 8];
+  blake2b_init(out, 64, blake2b_person(personal, 0), blake2b_person(personal, 1));
+  blake2b_compress(out, m, (uint64_t)len, true);
 }
 
 // 512-bit LE value mod r_J, canonical: lo R^2 + hi R^3 (Montgomery, R = 2^256), then out

@@ -21,6 +21,7 @@
 #pragma once
 #include "../../include/zg.h"  // ZG_TREE_SPROUT / ZG_TREE_SAPLING
 #include "zg_bingcd.h"
+#include "zg_hash.h"  // sha256_compress_words
 #include "zg_jubjub.h"
 
 namespace zg {
@@ -160,63 +161,6 @@ ZG_INL void ph_merkle(const uint32_t* lw, const uint32_t* rw, int depth, const u
   const Fr x = fr_from_mont(fr_mul(acc.X, fr_inv_vt(acc.Z)));
 #pragma unroll
   for (int i = 0; i < 8; i++) out[i] = x.l[i];
-}
-
-// ---- SHA-256 compression of one 64-byte block (no padding), FIPS 180-4 section 6.2.2
-__device__ __constant__ const uint32_t ZG_SHA256_K[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-
-__device__ __forceinline__ uint32_t sha_rotr(uint32_t x, int k) { return (x >> k) | (x << (32 - k)); }
-
-// lw, rw: the 32 + 32 message bytes as LE words (byte order of H256); out likewise
-__device__ __forceinline__ void sha256_compress_words(const uint32_t* lw, const uint32_t* rw, uint32_t* out) {
-  uint32_t w[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    w[i] = __builtin_bswap32(lw[i]);
-    w[8 + i] = __builtin_bswap32(rw[i]);
-  }
-  const uint32_t iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                          0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  uint32_t a = iv[0], b = iv[1], c = iv[2], d = iv[3], e = iv[4], f = iv[5], g = iv[6], h = iv[7];
-#pragma unroll
-  for (int t = 0; t < 64; t++) {
-    uint32_t wt;
-    if (t < 16) {
-      wt = w[t];
-    } else {
-      const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-      const uint32_t s0 = sha_rotr(w15, 7) ^ sha_rotr(w15, 18) ^ (w15 >> 3);
-      const uint32_t s1 = sha_rotr(w2, 17) ^ sha_rotr(w2, 19) ^ (w2 >> 10);
-      wt = w[t & 15] = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-    }
-    const uint32_t t1 = h + (sha_rotr(e, 6) ^ sha_rotr(e, 11) ^ sha_rotr(e, 25)) + ((e & f) ^ (~e & g)) +
-                        ZG_SHA256_K[t] + wt;
-    const uint32_t t2 = (sha_rotr(a, 2) ^ sha_rotr(a, 13) ^ sha_rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + t2;
-  }
-  out[0] = __builtin_bswap32(iv[0] + a);
-  out[1] = __builtin_bswap32(iv[1] + b);
-  out[2] = __builtin_bswap32(iv[2] + c);
-  out[3] = __builtin_bswap32(iv[3] + d);
-  out[4] = __builtin_bswap32(iv[4] + e);
-  out[5] = __builtin_bswap32(iv[5] + f);
-  out[6] = __builtin_bswap32(iv[6] + g);
-  out[7] = __builtin_bswap32(iv[7] + h);
 }
 
 // LANES lanes per hash: Pedersen on a group (8 or 32), SHA-256 on one lane (LANES = 1)

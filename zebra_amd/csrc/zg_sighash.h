@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "zg_hash.h"
 #include "zg_txparse.h"
 
 #define ZG_SH_HD __host__ __device__ __forceinline__
@@ -47,17 +48,13 @@ ZG_SH_HD void seg_compact(ShSeg& s, uint32_t v) {
 }
 
 // ---- SHA-256 (FIPS 180-4), the block as big-endian words in a shift register
-ZG_SH_HD uint32_t sh_rotr32(uint32_t x, int k) { return (x >> k) | (x << (32 - k)); }
-ZG_SH_HD uint64_t sh_rotr64(uint64_t x, int k) { return (x >> k) | (x << (64 - k)); }
-
 struct ShSha256 {
   typedef uint32_t word;
   static constexpr uint32_t WB = 4;
   uint32_t st[8], w[16], cnt;
 
   ZG_SH_HD void init() {
-    st[0] = 0x6a09e667u, st[1] = 0xbb67ae85u, st[2] = 0x3c6ef372u, st[3] = 0xa54ff53au;
-    st[4] = 0x510e527fu, st[5] = 0x9b05688cu, st[6] = 0x1f83d9abu, st[7] = 0x5be0cd19u;
+    sha256_iv(st);
     cnt = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) w[i] = 0;
@@ -76,41 +73,13 @@ struct ShSha256 {
     acc = x & ((1u << (8 * nb)) - 1u);
     return (uint32_t)(t >> (8 * nb));
   }
-  ZG_SH_HD void compress() {
-    constexpr uint32_t K[64] = {
-        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-        0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-        0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-        0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-        0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-        0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-        0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-        0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-    uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-    for (int t = 0; t < 64; t++) {
-      uint32_t wt;
-      if (t < 16) {
-        wt = w[t];
-      } else {
-        const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-        const uint32_t s0 = sh_rotr32(w15, 7) ^ sh_rotr32(w15, 18) ^ (w15 >> 3);
-        const uint32_t s1 = sh_rotr32(w2, 17) ^ sh_rotr32(w2, 19) ^ (w2 >> 10);
-        wt = w[t & 15] = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-      }
-      const uint32_t t1 = h + (sh_rotr32(e, 6) ^ sh_rotr32(e, 11) ^ sh_rotr32(e, 25)) + ((e & f) ^ (~e & g)) + K[t] + wt;
-      const uint32_t t2 = (sh_rotr32(a, 2) ^ sh_rotr32(a, 13) ^ sh_rotr32(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-      h = g, g = f, f = e, e = d + t1, d = c, c = b, b = a, a = t1 + t2;
-    }
-    st[0] += a, st[1] += b, st[2] += c, st[3] += d, st[4] += e, st[5] += f, st[6] += g, st[7] += h;
-  }
   // `last` is unused: the padding makes the stream a whole number of blocks, each compressed as it fills
   ZG_SH_HD void push(uint32_t x, bool) {
 #pragma unroll
     for (int i = 0; i < 15; i++) w[i] = w[i + 1];
     w[15] = x;
     if (++cnt == 16) {
-      compress();
+      sha256_compress(st, w);
       cnt = 0;
     }
   }
@@ -134,9 +103,8 @@ struct ShSha256 {
     for (int i = 0; i < 8; i++) w[i] = st[i], w[8 + i] = 0;
     w[8] = 0x80000000u;
     w[15] = 256;
-    st[0] = 0x6a09e667u, st[1] = 0xbb67ae85u, st[2] = 0x3c6ef372u, st[3] = 0xa54ff53au;
-    st[4] = 0x510e527fu, st[5] = 0x9b05688cu, st[6] = 0x1f83d9abu, st[7] = 0x5be0cd19u;
-    compress();
+    sha256_iv(st);
+    sha256_compress(st, w);
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       out[4 * i] = (uint8_t)(st[i] >> 24), out[4 * i + 1] = (uint8_t)(st[i] >> 16);
@@ -155,9 +123,7 @@ struct ShBlake2b {
   uint32_t cnt, blocks;
 
   ZG_SH_HD void init(uint64_t p0, uint64_t p1) {
-    h[0] = 0x6a09e667f3bcc908ull ^ 0x01010020ull, h[1] = 0xbb67ae8584caa73bull, h[2] = 0x3c6ef372fe94f82bull;
-    h[3] = 0xa54ff53a5f1d36f1ull, h[4] = 0x510e527fade682d1ull, h[5] = 0x9b05688c2b3e6c1full;
-    h[6] = 0x1f83d9abfb41bd6bull ^ p0, h[7] = 0x5be0cd19137e2179ull ^ p1;
+    blake2b_init(h, 32, p0, p1);
     cnt = 0, blocks = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) m[i] = 0;
@@ -173,49 +139,11 @@ struct ShBlake2b {
     acc = nb ? x >> (64 - 8 * nb) : 0;
     return w;
   }
-  ZG_SH_HD void compress(uint64_t t, bool last) {
-    constexpr uint8_t S[12][16] = {
-        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
-        {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
-        {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
-        {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
-        {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
-        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
-    uint64_t v[16];
-#pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = h[i];
-    v[8] = 0x6a09e667f3bcc908ull, v[9] = 0xbb67ae8584caa73bull, v[10] = 0x3c6ef372fe94f82bull;
-    v[11] = 0xa54ff53a5f1d36f1ull, v[12] = 0x510e527fade682d1ull ^ t, v[13] = 0x9b05688c2b3e6c1full;
-    v[14] = 0x1f83d9abfb41bd6bull ^ (last ? ~0ull : 0ull), v[15] = 0x5be0cd19137e2179ull;
-#define ZG_SH_G(a, b, c, d, x, y)          \
-  v[a] = v[a] + v[b] + (x);                \
-  v[d] = sh_rotr64(v[d] ^ v[a], 32);       \
-  v[c] = v[c] + v[d];                      \
-  v[b] = sh_rotr64(v[b] ^ v[c], 24);       \
-  v[a] = v[a] + v[b] + (y);                \
-  v[d] = sh_rotr64(v[d] ^ v[a], 16);       \
-  v[c] = v[c] + v[d];                      \
-  v[b] = sh_rotr64(v[b] ^ v[c], 63);
-#pragma unroll
-    for (int r = 0; r < 12; r++) {
-      ZG_SH_G(0, 4, 8, 12, m[S[r][0]], m[S[r][1]])
-      ZG_SH_G(1, 5, 9, 13, m[S[r][2]], m[S[r][3]])
-      ZG_SH_G(2, 6, 10, 14, m[S[r][4]], m[S[r][5]])
-      ZG_SH_G(3, 7, 11, 15, m[S[r][6]], m[S[r][7]])
-      ZG_SH_G(0, 5, 10, 15, m[S[r][8]], m[S[r][9]])
-      ZG_SH_G(1, 6, 11, 12, m[S[r][10]], m[S[r][11]])
-      ZG_SH_G(2, 7, 8, 13, m[S[r][12]], m[S[r][13]])
-      ZG_SH_G(3, 4, 9, 14, m[S[r][14]], m[S[r][15]])
-    }
-#undef ZG_SH_G
-#pragma unroll
-    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
-  }
   // `last`: x is no word of the stream but the end of it; total: the message length
   ZG_SH_HD void push(uint64_t x, bool last, uint32_t total = 0) {
     if (cnt == 16 || last) {
       if (!last) blocks++;
-      compress(last ? (uint64_t)total : (uint64_t)blocks * 128u, last);
+      blake2b_compress(h, m, last ? (uint64_t)total : (uint64_t)blocks * 128u, last);
       cnt = 0;
     }
     if (!last) {
