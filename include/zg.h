@@ -348,6 +348,76 @@ int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_o
                const uint32_t* script_off, const uint64_t* amount, const uint32_t* hashtype, uint8_t* tx_status,
                uint8_t* hashes, uint8_t* status);
 
+/* ---- block bodies on the GPU: the transaction ids, the merkle root and the checks
+ * of BlockVerifier::check, one call per import window. Device memory per call; n = 0 / nblk = 0 and the
+ * argument checks as zg_headers_verify. zg_last_sig_kernel_ms covers the kernels of zg_txids and
+ * zg_blocks_verify.
+ *   zg_block_layout <- Block::deserialize chain/src/block.rs:10-14 over the exact slice block[0..len): the
+ *        1487-byte header (bytes 140..142 must be fd 40 05, as ZG_HDR_MALFORMED), a compact transaction
+ *        count, the transactions back to back, each by zg_tx_layout's rules. CPU, no context: the parser
+ *        zg_blocks_verify runs per block. -> ZG_TX_* (ZG_E_INVAL for a null pointer or len > 2^31):
+ *          ZG_TX_MALFORMED     truncated anywhere, a bad solution prefix, a malformed transaction, a count
+ *                              whose transactions cannot fit what is left, bytes left over
+ *          ZG_TX_NONCANONICAL  parses, but some compact size (the transaction count included) is not the
+ *                              shortest form: reported and left to the caller, as in zg_sighash
+ *        out, 6 values (0 when MALFORMED): [0] transactions, [1] IndexedBlock::size
+ *        (chain/src/indexed_block.rs:56-61: len for a canonical block, what the writer would emit
+ *        otherwise), [2] the sum of transaction_sigops(tx, NoopStore, false) as called at
+ *        verification/src/verify_block.rs:163-168 (verification/src/sigops.rs:9-41 over
+ *        Script::sigops_count(false) script/src/script.rs:289-317, Script::get_instruction :199-236 and
+ *        Opcode::from_u8 script/src/opcode.rs: CHECKSIG(VERIFY) 1, CHECKMULTISIG(VERIFY) 20; a script's
+ *        count stops at the first byte from_u8 does not know or the first push past its end; a
+ *        coinbase's input script is not counted), [3] 1 when transaction 0 is a coinbase
+ *        (Transaction::is_coinbase chain/src/transaction.rs:153-155, OutPoint::is_null :44-46), [4] the
+ *        index of the first later coinbase or UINT64_MAX, [5] bytes consumed. tx_off optional: out[0] + 1
+ *        offsets of the transactions from the block's first byte, written only when tx_off_cap >=
+ *        out[0] + 1.
+ *   zg_txids <- IndexedTransaction::hash chain/src/read_and_hash.rs:16-32 / transaction_hash: n slices of
+ *        one arena (slice i the bytes [off[i], off[i+1]), n + 1 offsets, not decreasing, at most 2^31
+ *        bytes in all, any length, 0 included) -> hashes n x 32: dhash256 of each slice, H256 storage
+ *        order. Slices of at least ZG_TXID_HOST_MIN bytes (environment at zg_create; default 65,536;
+ *        0: never) are hashed by the same routine on host threads while the kernel runs.
+ *   zg_blocks_verify <- BlockVerifier::check verification/src/verify_block.rs:31-40 (run first by
+ *        ChainVerifier::check verification/src/verify_chain.rs:35-42), with merkle_root
+ *        chain/src/merkle_root.rs:14-38 over the ids (IndexedBlock::merkle_root
+ *        chain/src/indexed_block.rs:63-65). blocks: nblk serialized blocks back to back, block b the bytes
+ *        [blk_off[b], blk_off[b+1]) (at most 2^20 blocks, 2^31 bytes); max_block_size / max_block_sigops:
+ *        consensus.max_block_size() / .max_block_sigops(); txid_cap: the capacity of txids in
+ *        transactions (ignored when txids is NULL).
+ *        -> status nblk: ZG_BLK_*, the first failing check in the reference's order (MALFORMED and
+ *        NONCANONICAL as zg_block_layout, before any check); flags optional nblk: ZG_BLK_F_* of every check
+ *        that fails, each evaluated on its own whatever the status (0 for a MALFORMED or NONCANONICAL
+ *        block; the merkle root of an EMPTY block is not evaluated: the reference's does not terminate);
+ *        detail optional nblk: the size for ZG_BLK_SIZE, the transaction index for ZG_BLK_EXTRA_COINBASE,
+ *        else 0; roots optional nblk x 32: the computed merkle root, H256 storage order (zero when not
+ *        hashed); tx_count nblk + 1: cumulative transaction counts, block b's ids being rows
+ *        [tx_count[b], tx_count[b+1]) of txids (optional, x 32). MALFORMED, NONCANONICAL and EMPTY blocks
+ *        contribute no rows and are not hashed. ZG_E_NOMEM: tx_count[nblk] > txid_cap; tx_count is filled
+ *        in, nothing else is written and nothing is hashed. Uniqueness (verify_block.rs:140-147) is
+ *        settled on the host from the ids. */
+#define ZG_BLK_OK 0
+#define ZG_BLK_MALFORMED 1       /* Block::deserialize fails */
+#define ZG_BLK_NONCANONICAL 2
+#define ZG_BLK_EMPTY 3           /* Error::Empty */
+#define ZG_BLK_COINBASE 4        /* Error::Coinbase */
+#define ZG_BLK_SIZE 5            /* Error::Size(size) */
+#define ZG_BLK_EXTRA_COINBASE 6  /* Error::Transaction(index, TransactionError::MisplacedCoinbase) */
+#define ZG_BLK_DUPLICATED 7      /* Error::DuplicatedTransactions */
+#define ZG_BLK_SIGOPS 8          /* Error::MaximumSigops */
+#define ZG_BLK_MERKLE_ROOT 9     /* Error::MerkleRoot */
+#define ZG_BLK_F_EMPTY 1
+#define ZG_BLK_F_COINBASE 2
+#define ZG_BLK_F_SIZE 4
+#define ZG_BLK_F_EXTRA_COINBASE 8
+#define ZG_BLK_F_DUPLICATED 16
+#define ZG_BLK_F_SIGOPS 32
+#define ZG_BLK_F_MERKLE_ROOT 64
+int zg_block_layout(const uint8_t* block, size_t len, uint64_t* out, uint64_t* tx_off, size_t tx_off_cap);
+int zg_txids(zg_ctx* ctx, size_t n, const uint8_t* arena, const uint64_t* off, uint8_t* hashes);
+int zg_blocks_verify(zg_ctx* ctx, size_t nblk, const uint8_t* blocks, const uint64_t* blk_off, uint64_t max_block_size,
+                     uint64_t max_block_sigops, size_t txid_cap, uint8_t* status, uint8_t* flags, uint64_t* detail,
+                     uint8_t* roots, uint64_t* tx_count, uint8_t* txids);
+
 /* ---- block headers on the GPU: the Equihash solution, the block hash and the
  * proof of work of HeaderVerifier::check (verification/src/verify_header.rs:26-32), batched. Any n
  * (zg_headers_verify: up to 2^20 headers per call); device memory per call, n = 0 and the argument

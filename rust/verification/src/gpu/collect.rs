@@ -179,6 +179,12 @@ pub trait Backend {
     /// header statuses (ZG_HDR_*: the first failing of deserialize / Equihash / proof of work) for
     /// serialized 1487-byte headers against the compact `max_bits`
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError>;
+    /// BlockVerifier::check (verify_block.rs:31-40) over the window's serialized blocks in one call ->
+    /// per block (status ZG_BLK_*: the first failing check in the reference's order, the detail word:
+    /// the size for ZG_BLK_SIZE, the index for ZG_BLK_EXTRA_COINBASE, the transaction ids in H256
+    /// storage order: none for a block that was not hashed)
+    fn blocks_verify(&self, blocks: &[Vec<u8>], max_block_size: u64, max_block_sigops: u64)
+                     -> Result<Vec<(u8, u64, Vec<[u8; 32]>)>, GpuError>;
     /// a window's public-input preparation in one call (zg_prep_batch: kinds ZG_PREP_KIND_*, fields
     /// n x ZG_PREP_FIELD_BYTES) -> Some((inputs n x 288 B, codes ZG_PREP_*)); None: the backend has no
     /// batched form and the window is prepared with the per-description host functions
@@ -211,6 +217,10 @@ impl Backend for GpuVerifier {
     }
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
         Ok(GpuVerifier::headers_verify(self, headers, max_bits)?.into_iter().map(|r| r.0).collect())
+    }
+    fn blocks_verify(&self, blocks: &[Vec<u8>], max_block_size: u64, max_block_sigops: u64)
+                     -> Result<Vec<(u8, u64, Vec<[u8; 32]>)>, GpuError> {
+        GpuVerifier::blocks_verify(self, blocks, max_block_size, max_block_sigops)
     }
     fn prep_batch(&self, kinds: &[u8], fields: &[u8]) -> Result<Option<(Vec<u8>, Vec<u8>)>, GpuError> {
         Ok(Some(GpuVerifier::prep_batch(self, kinds, fields)?))

@@ -28,6 +28,8 @@ use crypto::sapling_crypto::redjubjub::{self, Signature};
 use crypto::{pghr13_verify, Groth16VerifyingKey, Pghr13Proof, Pghr13VerifyingKey, JUBJUB};
 
 use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_MALFORMED, ZG_HDR_OK, ZG_HDR_POW};
+use super::ffi::{ZG_BLK_COINBASE, ZG_BLK_DUPLICATED, ZG_BLK_EMPTY, ZG_BLK_EXTRA_COINBASE, ZG_BLK_MALFORMED,
+                 ZG_BLK_MERKLE_ROOT, ZG_BLK_OK, ZG_BLK_SIGOPS, ZG_BLK_SIZE};
 use super::ffi::{ZG_ECDSA_OK, ZG_ECDSA_PUBLIC, ZG_ECDSA_SIGNATURE, ZG_ECDSA_SIGNATURE_ENCODING};
 use super::ffi::{ZG_SIGHASH_INPUT_RANGE, ZG_SIGHASH_OK, ZG_SIGHASH_TX_MALFORMED, ZG_TX_MALFORMED, ZG_TX_OK};
 use super::ffi::{ZG_ED_OK, ZG_ED_PUBLIC_ENCODING, ZG_ED_SIGNATURE, ZG_ED_SIGNATURE_ENCODING, ZG_GEN_BINDING,
@@ -231,6 +233,35 @@ impl<'a> super::collect::Backend for CpuBackend<'a> {
                     return ZG_HDR_POW;
                 }
                 ZG_HDR_OK
+            })
+            .collect())
+    }
+
+    /// the reference's own BlockVerifier::check, its error as ZG_BLK_* with the detail word; the ids are
+    /// the IndexedTransaction hashes
+    fn blocks_verify(&self, blocks: &[Vec<u8>], _max_block_size: u64, _max_block_sigops: u64)
+                     -> Result<Vec<(u8, u64, Vec<[u8; 32]>)>, GpuError> {
+        use error::{Error, TransactionError};
+        // max_block_size() and max_block_sigops() are the same constants on every network (consensus.rs:345-351)
+        let consensus = ::network::ConsensusParams::new(::network::Network::Mainnet);
+        Ok(blocks
+            .par_iter()
+            .map(|raw| {
+                let block: ::chain::IndexedBlock = match ::ser::deserialize::<_, ::chain::Block>(&raw[..]) {
+                    Ok(b) => b.into(),
+                    Err(_) => return (ZG_BLK_MALFORMED, 0, Vec::new()),
+                };
+                let ids = block.transactions.iter().map(|t| *t.hash).collect();
+                match ::verify_block::BlockVerifier::new(&block, &consensus).check() {
+                    Ok(()) => (ZG_BLK_OK, 0, ids),
+                    Err(Error::Empty) => (ZG_BLK_EMPTY, 0, ids),
+                    Err(Error::Coinbase) => (ZG_BLK_COINBASE, 0, ids),
+                    Err(Error::Size(size)) => (ZG_BLK_SIZE, size as u64, ids),
+                    Err(Error::Transaction(i, TransactionError::MisplacedCoinbase)) => (ZG_BLK_EXTRA_COINBASE, i as u64, ids),
+                    Err(Error::DuplicatedTransactions) => (ZG_BLK_DUPLICATED, 0, ids),
+                    Err(Error::MaximumSigops) => (ZG_BLK_SIGOPS, 0, ids),
+                    Err(_) => (ZG_BLK_MERKLE_ROOT, 0, ids),
+                }
             })
             .collect())
     }

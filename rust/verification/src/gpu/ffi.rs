@@ -79,6 +79,25 @@ pub const ZG_SIGHASH_TX_MALFORMED: u8 = 1;
 pub const ZG_SIGHASH_TX_NONCANONICAL: u8 = 2;
 pub const ZG_SIGHASH_INPUT_RANGE: u8 = 3;
 pub const ZG_SIGHASH_NO_INPUT: u32 = 0xFFFF_FFFF;
+// zg_blocks_verify: the first failing check of BlockVerifier::check (after the parser's two verdicts), and
+// the flags of every check that fails
+pub const ZG_BLK_OK: u8 = 0;
+pub const ZG_BLK_MALFORMED: u8 = 1;
+pub const ZG_BLK_NONCANONICAL: u8 = 2;
+pub const ZG_BLK_EMPTY: u8 = 3;
+pub const ZG_BLK_COINBASE: u8 = 4;
+pub const ZG_BLK_SIZE: u8 = 5;
+pub const ZG_BLK_EXTRA_COINBASE: u8 = 6;
+pub const ZG_BLK_DUPLICATED: u8 = 7;
+pub const ZG_BLK_SIGOPS: u8 = 8;
+pub const ZG_BLK_MERKLE_ROOT: u8 = 9;
+pub const ZG_BLK_F_EMPTY: u8 = 1;
+pub const ZG_BLK_F_COINBASE: u8 = 2;
+pub const ZG_BLK_F_SIZE: u8 = 4;
+pub const ZG_BLK_F_EXTRA_COINBASE: u8 = 8;
+pub const ZG_BLK_F_DUPLICATED: u8 = 16;
+pub const ZG_BLK_F_SIGOPS: u8 = 32;
+pub const ZG_BLK_F_MERKLE_ROOT: u8 = 64;
 // zg_equihash_verify instances, zg_headers_verify statuses (the first failing check) and flags (every check)
 pub const ZG_EQ_200_9: c_int = 0;
 pub const ZG_EQ_96_5: c_int = 1;
@@ -164,6 +183,12 @@ extern "C" {
                       n: usize, item_tx: *const u32, input_index: *const u32, scripts: *const u8,
                       script_off: *const u32, amount: *const u64, hashtype: *const u32, tx_status: *mut u8,
                       hashes: *mut u8, status: *mut u8) -> c_int;
+    pub fn zg_block_layout(block: *const u8, len: usize, out: *mut u64, tx_off: *mut u64, tx_off_cap: usize) -> c_int;
+    pub fn zg_txids(ctx: *mut ZgCtx, n: usize, arena: *const u8, off: *const u64, hashes: *mut u8) -> c_int;
+    pub fn zg_blocks_verify(ctx: *mut ZgCtx, nblk: usize, blocks: *const u8, blk_off: *const u64,
+                            max_block_size: u64, max_block_sigops: u64, txid_cap: usize, status: *mut u8,
+                            flags: *mut u8, detail: *mut u64, roots: *mut u8, tx_count: *mut u64,
+                            txids: *mut u8) -> c_int;
     pub fn zg_last_sig_kernel_ms(ctx: *mut ZgCtx, ms: *mut f32) -> c_int;
     pub fn zg_equihash_verify(ctx: *mut ZgCtx, params: c_int, n: usize, inputs: *const u8, input_len: usize,
                               solutions: *const u8, ok: *mut u8, repeated: *mut u8) -> c_int;

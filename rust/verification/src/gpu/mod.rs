@@ -347,6 +347,43 @@ impl GpuVerifier {
             .collect())
     }
 
+    /// BlockVerifier::check (verify_block.rs:31-40) over serialized blocks in ONE call (zg_blocks_verify)
+    /// -> per block (status ZG_BLK_*, detail word, transaction ids in H256 storage order). The id buffer
+    /// is sized from the bytes: no transaction is shorter than 10 bytes.
+    pub fn blocks_verify(&self, blocks: &[Vec<u8>], max_block_size: u64, max_block_sigops: u64)
+                         -> Result<Vec<(u8, u64, Vec<[u8; 32]>)>, GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let n = blocks.len();
+        let mut off = vec![0u64; n + 1];
+        for (i, b) in blocks.iter().enumerate() {
+            off[i + 1] = off[i] + b.len() as u64;
+        }
+        let mut flat: Vec<u8> = blocks.iter().flat_map(|b| b.iter().cloned()).collect();
+        flat.push(0);
+        let cap = flat.len() / 10 + 1;
+        let mut status = vec![0u8; n.max(1)];
+        let mut detail = vec![0u64; n.max(1)];
+        let mut counts = vec![0u64; n + 1];
+        let mut ids = vec![0u8; 32 * cap];
+        check(self.ctx, unsafe {
+            ffi::zg_blocks_verify(self.ctx, n, flat.as_ptr(), off.as_ptr(), max_block_size, max_block_sigops, cap,
+                                  status.as_mut_ptr(), std::ptr::null_mut(), detail.as_mut_ptr(), std::ptr::null_mut(),
+                                  counts.as_mut_ptr(), ids.as_mut_ptr())
+        })?;
+        Ok((0..n)
+            .map(|b| {
+                let rows = (counts[b] as usize..counts[b + 1] as usize)
+                    .map(|r| {
+                        let mut h = [0u8; 32];
+                        h.copy_from_slice(&ids[32 * r..32 * r + 32]);
+                        h
+                    })
+                    .collect();
+                (status[b], detail[b], rows)
+            })
+            .collect())
+    }
+
     /// PHGR JoinSplit proofs (sprout.rs:61-67): per item the 296-byte proof and its
     /// into_bn_frs inputs (`prep_joinsplit_bn`) -> ZG_STATUS_* (DECODE_INVALID = InvalidEncoding,
     /// VERIFY_FAILED = InvalidPGHRProof). The builtin res/sprout-verifying-key.json is loaded on

@@ -23,6 +23,13 @@
 //! `precheck` fails at append still has its header verified with the window it flushes, and a
 //! header error outranks its `precheck` error. Without a header nothing changes.
 //!
+//! Block bodies: a block that returns its whole serialization from
+//! `ImportBlock::raw` has BlockVerifier::check (verify_block.rs:31-40) deferred too: the window's
+//! serialized blocks go through ONE `Backend::blocks_verify` call when the window is verified. Per
+//! block the order is the reference's (verify_chain.rs:35-42): the BlockVerifier error comes before
+//! that block's header error and before its transaction errors, and still after a `header_precheck`
+//! failure raised at append. The writer keeps the returned ids (`txids`). Without `raw` nothing changes.
+//!
 //! Contract (as in the Python original): identical storage and first error for a caller that
 //! stops at the first error -- the reference's only caller, zebra/commands/import.rs:20-28,
 //! returns on any Err.
@@ -30,6 +37,8 @@ use std::collections::{HashMap, HashSet, VecDeque};
 
 use super::collect::{verify_block, Backend, Tx, TxError};
 use super::ffi::{ZG_HDR_EQUIHASH, ZG_HDR_OK, ZG_HDR_POW};
+use super::ffi::{ZG_BLK_COINBASE, ZG_BLK_DUPLICATED, ZG_BLK_EMPTY, ZG_BLK_EXTRA_COINBASE, ZG_BLK_MERKLE_ROOT,
+                 ZG_BLK_NONCANONICAL, ZG_BLK_OK, ZG_BLK_SIGOPS, ZG_BLK_SIZE};
 use super::GpuError;
 
 /// sync/src/blocks_writer.rs:20
@@ -61,6 +70,11 @@ pub trait ImportBlock {
     /// the 1487 serialized header bytes when the writer is to verify the Equihash solution and the
     /// proof of work; None: the caller ran HeaderVerifier::check itself, inside `precheck`
     fn header(&self) -> Option<&[u8]> {
+        None
+    }
+    /// the whole serialized block when the writer is to run BlockVerifier::check (verify_block.rs:31-40);
+    /// None: the caller ran it itself, inside `precheck`
+    fn raw(&self) -> Option<&[u8]> {
         None
     }
     /// the header checks that precede the Equihash solution (HeaderVersion::check), run at append
@@ -116,6 +130,29 @@ pub struct DeferredBlocksWriter<'a, S: BlockStore<B>, B: ImportBlock, V: Backend
     pending: HashSet<[u8; 32]>,
     window_proofs: usize,
     max_bits: u32,
+    max_block_size: u64,
+    max_block_sigops: u64,
+    /// block hash -> its transaction ids (H256 storage order), of the blocks whose body was verified here
+    pub txids: HashMap<[u8; 32], Vec<[u8; 32]>>,
+}
+
+/// ConsensusParams::max_block_size / max_block_sigops (network/src/consensus.rs:345-351)
+pub const MAX_BLOCK_SIZE: u64 = 2_000_000;
+pub const MAX_BLOCK_SIGOPS: u64 = 20_000;
+
+/// zg_blocks_verify status -> the reference's error, with the call's detail word
+fn block_error(status: u8, detail: u64) -> String {
+    match status {
+        ZG_BLK_NONCANONICAL => "NoncanonicalBlock".to_string(),
+        ZG_BLK_EMPTY => "Empty".to_string(),
+        ZG_BLK_COINBASE => "Coinbase".to_string(),
+        ZG_BLK_SIZE => format!("Size({})", detail),
+        ZG_BLK_EXTRA_COINBASE => format!("Transaction({}, MisplacedCoinbase)", detail),
+        ZG_BLK_DUPLICATED => "DuplicatedTransactions".to_string(),
+        ZG_BLK_SIGOPS => "MaximumSigops".to_string(),
+        ZG_BLK_MERKLE_ROOT => "MerkleRoot".to_string(),
+        _ => "MalformedBlock".to_string(),
+    }
 }
 
 /// headers per window: a window of header-carrying blocks is verified at the latest when it holds this many
@@ -143,6 +180,9 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
             pending: HashSet::new(),
             window_proofs: window_proofs.max(1),
             max_bits: MAINNET_MAX_BITS,
+            max_block_size: MAX_BLOCK_SIZE,
+            max_block_sigops: MAX_BLOCK_SIGOPS,
+            txids: HashMap::new(),
         }
     }
 
@@ -191,7 +231,7 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
                 // an earlier block of the window may hold the first error: verify those first --
                 // with this block's header, whose Equihash / Pow error comes before `e`
                 let backend = self.backend;
-                self.flush_on(backend, b.header())?;
+                self.flush_on(backend, b.header(), b.raw())?;
                 return Err(WriterError::Verification(e));
             }
             self.pending.insert(b.hash());
@@ -208,20 +248,47 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
     /// verify the window, insert its blocks up to the first failing one, return its error
     pub fn flush(&mut self) -> Result<(), WriterError> {
         let backend = self.backend;
-        self.flush_on(backend, None)
+        self.flush_on(backend, None, None)
     }
 
     /// after `WriterError::Backend`: verify the window the writer still holds on another backend
     /// (the CPU backend of cpu.rs), with the same insertion and first-error contract as `flush`
     pub fn flush_with<W: Backend>(&mut self, other: &W) -> Result<(), WriterError> {
-        self.flush_on(other, None)
+        self.flush_on(other, None, None)
     }
 
     /// tail: the header of a block that already failed its precheck and is not part of the window;
     /// it is verified with the window's headers and its error returned after the window's own
-    fn flush_on<W: Backend>(&mut self, backend: &W, tail: Option<&[u8]>) -> Result<(), WriterError> {
-        if self.window.is_empty() && tail.is_none() {
+    /// tail_raw: that block's serialization, verified with the window's bodies likewise
+    fn flush_on<W: Backend>(&mut self, backend: &W, tail: Option<&[u8]>, tail_raw: Option<&[u8]>)
+                            -> Result<(), WriterError> {
+        if self.window.is_empty() && tail.is_none() && tail_raw.is_none() {
             return Ok(());
+        }
+        // the bodies, ONE call; a block's BlockVerifier error comes before its header error
+        let mut with_raw = Vec::new();
+        let mut raws: Vec<Vec<u8>> = Vec::new();
+        for (i, r) in self.window.iter().map(|b| b.raw()).chain(std::iter::once(tail_raw)).enumerate() {
+            if let Some(r) = r {
+                with_raw.push(i);
+                raws.push(r.to_vec());
+            }
+        }
+        let mut bfail = usize::max_value();
+        let mut berr = None;
+        let mut ids: Vec<([u8; 32], Vec<[u8; 32]>)> = Vec::new();
+        if !raws.is_empty() {
+            let res = backend.blocks_verify(&raws, self.max_block_size, self.max_block_sigops).map_err(WriterError::Backend)?;
+            for (k, (status, detail, block_ids)) in res.into_iter().enumerate() {
+                if status != ZG_BLK_OK {
+                    bfail = with_raw[k];
+                    berr = Some(block_error(status, detail));
+                    break;
+                }
+                if with_raw[k] < self.window.len() {
+                    ids.push((self.window[with_raw[k]].hash(), block_ids));
+                }
+            }
         }
         // the headers first, ONE call: the first failing header bounds what else can matter
         let n_seq = self.window.len() + tail.is_some() as usize;
@@ -242,6 +309,11 @@ impl<'a, S: BlockStore<B>, B: ImportBlock, V: Backend> DeferredBlocksWriter<'a, 
                 herr = Some(header_error(sts[k]));
             }
         }
+        if berr.is_some() && bfail <= hfail {
+            hfail = bfail;
+            herr = berr;
+        }
+        self.txids.extend(ids);
         // the transactions of the blocks before the first failing header, flattened in block order
         // (one verify_block call)
         let mut owner = Vec::new();
@@ -364,6 +436,10 @@ mod tests {
         }
         fn headers_verify(&self, headers: &[Vec<u8>], _max_bits: u32) -> Result<Vec<u8>, GpuError> {
             Ok(vec![0; headers.len()])
+        }
+        fn blocks_verify(&self, blocks: &[Vec<u8>], _max_block_size: u64, _max_block_sigops: u64)
+                         -> Result<Vec<(u8, u64, Vec<[u8; 32]>)>, GpuError> {
+            Ok(blocks.iter().map(|_| (0, 0, Vec::new())).collect())
         }
     }
 

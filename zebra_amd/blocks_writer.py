@@ -30,6 +30,15 @@ transactions. A block whose `precheck` fails at append still has its header veri
 window it flushes, and a header error outranks its `precheck` error. With `header=None` nothing
 changes.
 
+Block bodies: a block that carries its whole serialization (`Block.raw`) has
+BlockVerifier::check (verification/src/verify_block.rs:31-40: empty, coinbase, size, extra coinbases,
+uniqueness, sigops, merkle root) deferred as well: the window's blocks that carry `raw` go through ONE
+zg_blocks_verify call when the window is verified. Per block the order is the reference's
+(verification/src/verify_chain.rs:35-42: block.check(), then the header, then the transactions): the
+BlockVerifier error comes before that block's header error and before its transaction errors, and still
+after a `header_precheck` failure raised at append. The writer keeps the transaction ids the call returns
+(`txids[block.hash]`), so the caller need not hash again. With `raw=None` nothing changes.
+
 Contract: the equivalence holds for a caller that stops at the first error, as the reference's
 only caller does (zebra/commands/import.rs:20-28 returns on any Err from append_block). The
 error of a block surfaces when its window is verified -- at that block's append_block or at a
@@ -47,6 +56,19 @@ MAINNET_MAX_BITS = 0x1f07ffff   # Network::Mainnet.max_bits() (network/src/netwo
 # zg_headers_verify status -> the reference's error (verification/src/error.rs); a header whose solution
 # does not deserialize never reaches the reference's writer
 HEADER_ERRORS = {1: "MalformedHeader", 2: "InvalidEquihashSolution", 3: "Pow"}
+# zg_blocks_verify status -> the reference's error; Size and the misplaced coinbase carry the call's detail
+# word. A block that does not deserialize never reaches the reference's writer; a non-canonical one (the
+# chain holds none) is reported as such
+BLOCK_ERRORS = {1: "MalformedBlock", 2: "NoncanonicalBlock", 3: "Empty", 4: "Coinbase", 5: "Size",
+                6: "MisplacedCoinbase", 7: "DuplicatedTransactions", 8: "MaximumSigops", 9: "MerkleRoot"}
+MAINNET_MAX_BLOCK_SIZE = 2000000     # ConsensusParams::max_block_size (network/src/consensus.rs)
+MAINNET_MAX_BLOCK_SIGOPS = 20000     # ConsensusParams::max_block_sigops
+
+
+def block_error(status, detail):
+    """Error::Size(size), Error::Transaction(index, MisplacedCoinbase), or the bare name"""
+    name = BLOCK_ERRORS[status]
+    return ("Size", detail) if status == 5 else ("Transaction", detail, name) if status == 6 else name
 
 
 class WriterError(Exception):
@@ -73,12 +95,13 @@ class Block:
     outcomes that are not proofs (scripts, tree roots, nullifiers, ...) are set on the collector
     Tx objects by the same caller."""
 
-    def __init__(self, hash, parent, txs, precheck=None, header=None, header_precheck=None):
-        """header: the 1487 serialized header bytes, or None (the caller ran HeaderVerifier::check itself,
+    def __init__(self, hash, parent, txs, precheck=None, header=None, header_precheck=None, raw=None):
+        """raw: the whole serialized block, or None (the caller ran BlockVerifier::check itself, inside
+        precheck); header: the 1487 serialized header bytes, or None (the caller ran HeaderVerifier::check itself,
         inside precheck); header_precheck(writer) -> None | error: the checks that precede the Equihash
         solution (HeaderVersion::check), run when the block is appended"""
         self.hash, self.parent, self.txs, self.precheck = hash, parent, txs, precheck
-        self.header, self.header_precheck = header, header_precheck
+        self.header, self.header_precheck, self.raw = header, header_precheck, raw
 
     def n_proofs(self):
         return sum(len(t.joinsplits) + len(t.spends) + len(t.outputs) for t in self.txs)
@@ -140,10 +163,13 @@ class DeferredBlocksWriter:
     verify_window(txs) -> None | (tx_index, error): the collector over the window's flattened
     transactions (default: collector.verify_block with `ctx`, i.e. one GPU batch).
     verify_headers(headers) -> list of HDR_* statuses: the window's headers in one call (default:
-    ctx.headers_verify against the compact `max_bits`, the network's proof-of-work limit)."""
+    ctx.headers_verify against the compact `max_bits`, the network's proof-of-work limit).
+    verify_blocks(raws) -> (list of BLK_* statuses, list of detail words, list of id lists): the window's
+    serialized blocks in one call (default: ctx.blocks_verify against `max_block_size` / `max_block_sigops`)."""
 
     def __init__(self, storage, ctx=None, verify_window=None, window_proofs=65536, verify_headers=None,
-                 max_bits=MAINNET_MAX_BITS, window_headers=16384):
+                 max_bits=MAINNET_MAX_BITS, window_headers=16384, verify_blocks=None,
+                 max_block_size=MAINNET_MAX_BLOCK_SIZE, max_block_sigops=MAINNET_MAX_BLOCK_SIGOPS):
         self.storage = storage
         self.orphans = _OrphanPool()
         self.window = []          # pending blocks in chain order (prechecked, not inserted)
@@ -161,6 +187,15 @@ class DeferredBlocksWriter:
                                        "nor verify_headers")
                 return ctx.headers_verify(headers, max_bits)[0]
         self.verify_headers = verify_headers
+        if verify_blocks is None:
+            def verify_blocks(raws):
+                if ctx is None:
+                    raise RuntimeError("a block carries its serialization but the writer has neither a context "
+                                       "nor verify_blocks")
+                st, _, detail, _, _, ids = ctx.blocks_verify(raws, max_block_size, max_block_sigops)
+                return st, detail, ids
+        self.verify_blocks = verify_blocks
+        self.txids = {}           # block hash -> its transaction ids, of the blocks whose body was verified here
 
     def _known(self, h):
         return h in self.pending or self.storage.contains(h)
@@ -185,7 +220,7 @@ class DeferredBlocksWriter:
                 # the block fails before its transactions are accepted; an earlier block of the
                 # window may hold the first error: verify (and accept) those first -- with this
                 # block's header, whose Equihash / Pow error comes before `pre`
-                self.flush(_tail=b if b.header is not None else None)
+                self.flush(_tail=b if b.header is not None or b.raw is not None else None)
                 raise WriterError("Verification", pre)
             self.window.append(b)
             self.pending.add(b.hash)
@@ -202,6 +237,17 @@ class DeferredBlocksWriter:
         blocks = self.window
         # the headers first, ONE call: the first failing header bounds what else can matter
         seq = blocks + ([_tail] if _tail is not None else [])
+        # the bodies, ONE call; a block's BlockVerifier error comes before its header error
+        with_raw = [i for i, b in enumerate(seq) if b.raw is not None]
+        bfail, berr, ids = len(seq), None, {}
+        if with_raw:
+            sts, details, idlists = self.verify_blocks([seq[i].raw for i in with_raw])
+            assert len(sts) == len(with_raw)
+            for k, i in enumerate(with_raw):
+                if sts[k] != 0:
+                    bfail, berr = i, block_error(sts[k], details[k])
+                    break
+                ids[seq[i].hash] = idlists[k]
         with_header = [i for i, b in enumerate(seq) if b.header is not None]
         hfail, herr = len(seq), None
         if with_header:
@@ -211,6 +257,8 @@ class DeferredBlocksWriter:
                 if st != 0:
                     hfail, herr = i, HEADER_ERRORS[st]
                     break
+        if bfail <= hfail and berr is not None:
+            hfail, herr = bfail, berr
         flat, owner = [], []
         for bi, b in enumerate(blocks[:hfail]):
             for ti, t in enumerate(b.txs):
@@ -220,6 +268,7 @@ class DeferredBlocksWriter:
         # and the pending set unchanged, so the caller can retry or re-run it on another backend
         res = self.verify_window(flat) if flat else None
         self.window, self.pending = [], set()
+        self.txids.update(ids)
         fail_block = len(blocks)
         err = None
         if res is not None:

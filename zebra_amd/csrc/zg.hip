@@ -9,6 +9,7 @@
 #include <sys/random.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -18,6 +19,7 @@
 
 #include "../../include/zg.h"
 #include "zg_blake2b.h"
+#include "zg_blocks.h"
 #include "zg_chacha.h"
 #include "zg_ecdsa.h"    // ZG_EC_COMB_*
 #include "zg_ed25519.h"  // ZG_ED_COMB_*
@@ -52,6 +54,8 @@ using namespace zg;
 #define ZG_LINES_LANE_MIN 32768  // straight-line R-chain from here (r03: 64k 14.93 -> 14.47 ms per batch in
                                  // flight; 16k 4.90 -> 5.14 and 8k 3.21 -> 3.63 favour the staged program)
 #define ZG_PGHR_CHUNK 65536      // proofs per batch check of zg_pghr13_verify (ZG_PGHR_CHUNK lowers it, 64 at the least)
+#define ZG_TXID_HOST_MIN 65536   // slices from this many bytes are hashed on host threads beside k_txid: a 100 KB
+                                 // transaction in a 65,536-transaction window, 15.5 -> 9.8 ms per call
 #define ZG_DEFAULT_PAIRS 8       // stream pairs per device (ZG_STREAM_PAIRS overrides, 1..16)
 #define ZG_HI_PAIRS 4            // high-priority stream pairs per device (zg_set_priority round-robin)
 
@@ -228,6 +232,8 @@ struct zg_ctx {
   int pghr_straus_b = 0;     // ZG_STRAUS_B: proofs per lane of k_pghr_straus, 1 / 2 / 4; 0 (any other value) by size
   int pghr_bseg_k = 0;       // ZG_BSEG_K: proofs per lane of k_pghr_bseg, 1..32 (larger: 32); 0 (or less) by size
   size_t pghr_chunk = ZG_PGHR_CHUNK;  // ZG_PGHR_CHUNK: proofs per batch check of one call, 64..65,536
+  size_t txid_host_min = ZG_TXID_HOST_MIN;  // ZG_TXID_HOST_MIN: slices of at least this many bytes are hashed on
+                                            // host threads beside k_txid; 0: never
   hipEvent_t sig_ev[2] = {};  // around the kernel of the last signature call (zg_last_sig_kernel_ms), first use
   float sig_ms = 0.0f;
 };
@@ -368,6 +374,7 @@ extern "C" zg_ctx* zg_create(const zg_config* cfg) {
   if (const char* e = getenv("ZG_LINES_LANE")) ctx->lines_lane = atoi(e);
   if (const char* e = getenv("ZG_TREE_COOP_BELOW")) ctx->coop_below = (size_t)atol(e);
   if (const char* e = getenv("ZG_DEBUG_EACH")) ctx->debug_each = atoi(e);
+  if (const char* e = getenv("ZG_TXID_HOST_MIN")) ctx->txid_host_min = (size_t)std::max(0l, atol(e));
   if (const char* e = getenv("ZG_STRAUS_B")) {
     const int v = atoi(e);
     ctx->pghr_straus_b = v == 1 || v == 2 || v == 4 ? v : 0;
@@ -822,6 +829,9 @@ hipError_t launch_sighash_digests(hipStream_t st, const uint8_t* arena, const Sh
 hipError_t launch_sighash_items(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
                                 const uint32_t* out_off, const uint8_t* digests, const uint8_t* scripts,
                                 const ShDevItem* items, int n, uint8_t* hashes);
+hipError_t launch_txid(hipStream_t st, const uint8_t* arena, const TxidSlice* slices, int n, uint8_t* out);  // zg_blocks.hip
+hipError_t launch_block_merkle(hipStream_t st, const uint8_t* arena, const MerkleBlk* blks, int nblk,
+                               const uint8_t* ids, uint8_t* ping, uint8_t* pong, uint8_t* roots, uint8_t* match);
 int equihash_solution_bytes(int params);                                                      // zg_equihash.hip
 hipError_t launch_equihash(hipStream_t st, int params, const uint8_t* inputs, size_t in_stride, int in_len,
                            const uint8_t* sols, size_t sol_stride, int n, uint8_t* ok, uint8_t* repeated);
@@ -1799,6 +1809,191 @@ extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uin
   HIPCHK(hipMemcpyAsync(hh.data(), dhash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(sig_sync(ctx));
   for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * sorted[k].slot, hh.data() + 32 * k, 32);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ block bodies (zg_blocks.h)
+// The slices of one call: the kernel's, longest first (a wave's lanes then run similar lengths and the
+// longest chains start first), and those of at least ZG_TXID_HOST_MIN bytes, which host threads hash beside it
+struct TxidPlan {
+  std::vector<TxidSlice> dev, host;
+};
+static void txid_plan(const zg_ctx* ctx, const std::vector<TxidSlice>& all, TxidPlan& P) {
+  for (const TxidSlice& s : all) (ctx->txid_host_min && s.len >= ctx->txid_host_min ? P.host : P.dev).push_back(s);
+  std::stable_sort(P.dev.begin(), P.dev.end(), [](const TxidSlice& a, const TxidSlice& b) { return a.len > b.len; });
+}
+// rows[32 k ..]: the hash of hs[k], by the kernel's routine on up to 16 threads (each slice copied under the
+// arena rule of zg_blocks.h: the caller's buffer is neither aligned nor padded)
+static void txid_host_rows(const uint8_t* arena, const std::vector<TxidSlice>& hs, std::vector<uint8_t>& rows) {
+  rows.assign(32 * hs.size() + 1, 0);
+  const size_t nt = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), hs.size()});
+  auto work = [&](size_t t) {
+    TxidArena tmp;
+    for (size_t k = t; k < hs.size(); k += nt) txid_hash_bytes(arena + hs[k].off, hs[k].len, tmp, &rows[32 * k]);
+  };
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nt; t++) th.emplace_back(work, t);
+  if (nt) work(0);
+  for (auto& t : th) t.join();
+}
+
+extern "C" int zg_txids(zg_ctx* ctx, size_t n, const uint8_t* arena, const uint64_t* off, uint8_t* hashes) {
+  if (!ctx || (n && (!arena || !off || !hashes)) || n > (1u << 30)) return ZG_E_INVAL;
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return ZG_E_INVAL;
+  if (n && off[n] - off[0] > (1ull << 31)) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!n) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint64_t base0 = off[0];
+  const size_t bytes = (size_t)(off[n] - base0);
+  std::vector<TxidSlice> all(n);
+  for (size_t i = 0; i < n; i++) all[i] = TxidSlice{(uint32_t)(off[i] - base0), (uint32_t)(off[i + 1] - off[i]), (uint32_t)i, 0};
+  TxidPlan P;
+  txid_plan(ctx, all, P);
+  DevScratch s;
+  uint8_t *darena, *dids;
+  TxidSlice* dsl;
+  HIPCHK(s.alloc(&darena, txid_arena_bytes(bytes)));
+  HIPCHK(s.alloc(&dids, 32 * n));
+  HIPCHK(s.alloc(&dsl, sizeof(TxidSlice) * (P.dev.size() + 1)));
+  if (bytes) HIPCHK(hipMemcpyAsync(darena, arena + base0, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (!P.dev.empty())
+    HIPCHK(hipMemcpyAsync(dsl, P.dev.data(), sizeof(TxidSlice) * P.dev.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] { return launch_txid(ctx->stream, darena, dsl, (int)P.dev.size(), dids); }));
+  std::vector<uint8_t> hrows;
+  txid_host_rows(arena + base0, P.host, hrows);  // while the kernel runs
+  HIPCHK(hipMemcpyAsync(hashes, dids, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(sig_sync(ctx));
+  for (size_t k = 0; k < P.host.size(); k++) memcpy(hashes + (size_t)32 * P.host[k].slot, &hrows[32 * k], 32);
+  return ZG_OK;
+}
+
+extern "C" int zg_blocks_verify(zg_ctx* ctx, size_t nblk, const uint8_t* blocks, const uint64_t* blk_off,
+                                uint64_t max_block_size, uint64_t max_block_sigops, size_t txid_cap, uint8_t* status,
+                                uint8_t* flags, uint64_t* detail, uint8_t* roots, uint64_t* tx_count, uint8_t* txids) {
+  if (!ctx || (nblk && (!blocks || !blk_off || !status || !tx_count)) || nblk > (1u << 20)) return ZG_E_INVAL;
+  for (size_t b = 0; b < nblk; b++)
+    if (blk_off[b + 1] < blk_off[b]) return ZG_E_INVAL;
+  if (nblk && blk_off[nblk] - blk_off[0] > (1ull << 31)) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (tx_count) tx_count[0] = 0;
+  if (!nblk) return ZG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint64_t base0 = blk_off[0];
+  const size_t bytes = (size_t)(blk_off[nblk] - base0);
+  DevScratch s;
+  uint8_t* darena;
+  HIPCHK(s.alloc(&darena, txid_arena_bytes(bytes)));
+  if (bytes) HIPCHK(hipMemcpyAsync(darena, blocks + base0, bytes, hipMemcpyHostToDevice, ctx->stream));
+
+  // the layouts, on host threads while the arena travels: every offset a lane follows is checked here
+  std::vector<BlockLayout> B(nblk);
+  std::vector<uint32_t> pst(nblk);
+  {
+    const size_t nt = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), nblk});
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+      for (size_t b; (b = next.fetch_add(1)) < nblk;)
+        pst[b] = block_layout(blocks + blk_off[b], (size_t)(blk_off[b + 1] - blk_off[b]), B[b]);
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+  }
+  std::vector<uint32_t> hb;  // the blocks that are hashed: parsed, canonical, not empty
+  for (size_t b = 0; b < nblk; b++) {
+    const bool hashed = pst[b] == ZG_TXP_OK && B[b].n_tx > 0;
+    if (hashed) hb.push_back((uint32_t)b);
+    tx_count[b + 1] = tx_count[b] + (hashed ? B[b].n_tx : 0);
+  }
+  const size_t total = (size_t)tx_count[nblk];
+  if (txids && total > txid_cap) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return fail(ctx, ZG_E_NOMEM, "zg_blocks_verify: the window holds more transactions than txid_cap");
+  }
+
+  std::vector<uint8_t> ids(32 * total + 1), hroots(32 * hb.size() + 1), hmatch(hb.size() + 1), hrows;
+  if (total) {
+    std::vector<TxidSlice> all;
+    std::vector<MerkleBlk> mb;
+    all.reserve(total);
+    for (uint32_t b : hb) {
+      const uint32_t o = (uint32_t)(blk_off[b] - base0);
+      mb.push_back(MerkleBlk{o, (uint32_t)tx_count[b], (uint32_t)B[b].n_tx, 0});
+      for (size_t t = 0; t < B[b].n_tx; t++)
+        all.push_back(TxidSlice{o + (uint32_t)B[b].tx_off[t], (uint32_t)(B[b].tx_off[t + 1] - B[b].tx_off[t]),
+                                (uint32_t)(tx_count[b] + t), 0});
+    }
+    TxidPlan P;
+    txid_plan(ctx, all, P);
+    uint8_t *dids, *dping, *dpong, *droots, *dmatch;
+    TxidSlice* dsl;
+    MerkleBlk* dmb;
+    HIPCHK(s.alloc(&dids, 32 * total));
+    HIPCHK(s.alloc(&dping, 32 * total));
+    HIPCHK(s.alloc(&dpong, 32 * total));
+    HIPCHK(s.alloc(&droots, 32 * mb.size()));
+    HIPCHK(s.alloc(&dmatch, mb.size()));
+    HIPCHK(s.alloc(&dsl, sizeof(TxidSlice) * (P.dev.size() + 1)));
+    HIPCHK(s.alloc(&dmb, sizeof(MerkleBlk) * mb.size()));
+    if (!P.dev.empty())
+      HIPCHK(hipMemcpyAsync(dsl, P.dev.data(), sizeof(TxidSlice) * P.dev.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dmb, mb.data(), sizeof(MerkleBlk) * mb.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(sig_timed(ctx, [&] {
+      hipError_t e = launch_txid(ctx->stream, darena, dsl, (int)P.dev.size(), dids);
+      if (e != hipSuccess) return e;
+      if (!P.host.empty()) {  // the host's share while k_txid runs; its rows join the kernel's before the trees
+        txid_host_rows(blocks + base0, P.host, hrows);
+        for (size_t k = 0; k < P.host.size() && e == hipSuccess; k++)
+          e = hipMemcpyAsync(dids + (size_t)32 * P.host[k].slot, &hrows[32 * k], 32, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return e;
+      }
+      return launch_block_merkle(ctx->stream, darena, dmb, (int)mb.size(), dids, dping, dpong, droots, dmatch);
+    }));
+    HIPCHK(hipMemcpyAsync(ids.data(), dids, 32 * total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hroots.data(), droots, 32 * mb.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hmatch.data(), dmatch, mb.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(sig_sync(ctx));
+  } else {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (txids && total) memcpy(txids, ids.data(), 32 * total);
+
+  // BlockVerifier::check's order (verify_block.rs:31-40); uniqueness from the ids, on the host
+  size_t h = 0;
+  std::vector<std::array<uint8_t, 32>> set;
+  for (size_t b = 0; b < nblk; b++) {
+    if (roots) memset(roots + 32 * b, 0, 32);
+    if (flags) flags[b] = 0;
+    if (detail) detail[b] = 0;
+    if (pst[b] != ZG_TXP_OK) {
+      status[b] = pst[b] == ZG_TXP_MALFORMED ? ZG_BLK_MALFORMED : ZG_BLK_NONCANONICAL;
+      continue;
+    }
+    const BlockLayout& L = B[b];
+    uint32_t f = 0;
+    if (L.n_tx == 0) f |= ZG_BLK_F_EMPTY;
+    if (!L.coinbase0) f |= ZG_BLK_F_COINBASE;
+    if (L.size > max_block_size) f |= ZG_BLK_F_SIZE;
+    if (L.extra_coinbase != BLOCK_NO_INDEX) f |= ZG_BLK_F_EXTRA_COINBASE;
+    if (L.sigops > max_block_sigops) f |= ZG_BLK_F_SIGOPS;
+    if (L.n_tx) {
+      set.resize((size_t)L.n_tx);
+      memcpy(set.data(), &ids[32 * (size_t)tx_count[b]], 32 * (size_t)L.n_tx);
+      std::sort(set.begin(), set.end());
+      if (std::adjacent_find(set.begin(), set.end()) != set.end()) f |= ZG_BLK_F_DUPLICATED;
+      if (!hmatch[h]) f |= ZG_BLK_F_MERKLE_ROOT;
+      if (roots) memcpy(roots + 32 * b, &hroots[32 * h], 32);
+      h++;
+    }
+    status[b] = f & ZG_BLK_F_EMPTY ? ZG_BLK_EMPTY : f & ZG_BLK_F_COINBASE ? ZG_BLK_COINBASE : f & ZG_BLK_F_SIZE ? ZG_BLK_SIZE
+              : f & ZG_BLK_F_EXTRA_COINBASE ? ZG_BLK_EXTRA_COINBASE : f & ZG_BLK_F_DUPLICATED ? ZG_BLK_DUPLICATED
+              : f & ZG_BLK_F_SIGOPS ? ZG_BLK_SIGOPS : f & ZG_BLK_F_MERKLE_ROOT ? ZG_BLK_MERKLE_ROOT : ZG_BLK_OK;
+    if (flags) flags[b] = (uint8_t)f;
+    if (detail) detail[b] = status[b] == ZG_BLK_SIZE ? L.size : status[b] == ZG_BLK_EXTRA_COINBASE ? L.extra_coinbase : 0;
+  }
   return ZG_OK;
 }
 

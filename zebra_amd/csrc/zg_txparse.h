@@ -33,6 +33,7 @@ struct TxReader {
   const uint8_t* d;
   size_t len, o = 0;
   bool bad = false, noncanonical = false;
+  uint64_t excess = 0;  // bytes the non-minimal compact sizes read so far take beyond their shortest forms
 
   size_t left() const { return len - o; }
   bool skip(uint64_t k) {
@@ -55,7 +56,10 @@ struct TxReader {
     const uint64_t b = le(1);
     if (bad || b < 0xfd) return b;
     const uint64_t v = le(b == 0xfd ? 2 : b == 0xfe ? 4 : 8);
-    if (b == 0xfd ? v < 0xfd : b == 0xfe ? v <= 0xffff : v <= 0xffffffffull) noncanonical = true;
+    if (b == 0xfd ? v < 0xfd : b == 0xfe ? v <= 0xffff : v <= 0xffffffffull) {
+      noncanonical = true;
+      excess += (b == 0xfd ? 3 : b == 0xfe ? 5 : 9) - (v < 0xfd ? 1 : v <= 0xffff ? 3 : v <= 0xffffffffull ? 5 : 9);
+    }
     return v;
   }
   // a list count: `min_size` bytes at least per element must still be there (checked before the caller
@@ -67,11 +71,13 @@ struct TxReader {
   }
 };
 
-// Parses tx[0..len), len <= 2^31. On ZG_TXP_OK fills L and appends n_in + 1 input offsets and n_out + 1
-// output offsets (the last of each: the end of the list) to in_off / out_off, L.in_idx / L.out_idx being
-// where they start. On any other status the two vectors are as they were.
-inline uint32_t tx_parse(const uint8_t* tx, size_t len, TxLayout& L, std::vector<uint32_t>& in_off,
-                         std::vector<uint32_t>& out_off) {
+// The one parser behind tx_parse and tx_parse_prefix. exact: the transaction must end where the slice
+// does; otherwise it ends where its last field does and L.consumed says where (the list counts are then
+// bounded by what is left of the slice, whatever follows the transaction in it). keep_nc: a
+// non-canonical transaction keeps its layout and its offsets like a canonical one. excess (optional):
+// the bytes its non-minimal compact sizes take beyond their shortest forms.
+inline uint32_t tx_parse_impl(const uint8_t* tx, size_t len, bool exact, bool keep_nc, TxLayout& L,
+                              std::vector<uint32_t>& in_off, std::vector<uint32_t>& out_off, uint64_t* excess) {
   const size_t in0 = in_off.size(), out0 = out_off.size();
   L = TxLayout{};
   TxReader r{tx, len};
@@ -135,14 +141,34 @@ inline uint32_t tx_parse(const uint8_t* tx, size_t len, TxLayout& L, std::vector
     if (L.n_js) r.skip(32 + 64);  // the pubkey and the signature
   }
   if (is_sap && (L.n_spend || L.n_sout)) r.skip(64);  // the binding signature
-  if (r.bad || r.o != len) return fail();
+  if (r.bad || (exact && r.o != len)) return fail();
   L.consumed = (uint32_t)r.o;
+  if (excess) *excess = r.excess;
   if (r.noncanonical) {
-    in_off.resize(in0);
-    out_off.resize(out0);
+    if (!keep_nc) {
+      in_off.resize(in0);
+      out_off.resize(out0);
+    }
     return ZG_TXP_NONCANONICAL;
   }
   return ZG_TXP_OK;
+}
+
+// Parses tx[0..len), len <= 2^31. On ZG_TXP_OK fills L and appends n_in + 1 input offsets and n_out + 1
+// output offsets (the last of each: the end of the list) to in_off / out_off, L.in_idx / L.out_idx being
+// where they start. On any other status the two vectors are as they were.
+inline uint32_t tx_parse(const uint8_t* tx, size_t len, TxLayout& L, std::vector<uint32_t>& in_off,
+                         std::vector<uint32_t>& out_off) {
+  return tx_parse_impl(tx, len, true, false, L, in_off, out_off, nullptr);
+}
+
+// The prefix form (zg_blocks.h: the transactions of a block lie back to back): the same rules over the
+// transaction that starts at p, of which `left` bytes of the block remain; it ends where its last field
+// does, L.consumed bytes on. A non-canonical transaction keeps its layout and offsets (the caller still
+// walks its scripts); *excess: see tx_parse_impl. On ZG_TXP_MALFORMED the two vectors are as they were.
+inline uint32_t tx_parse_prefix(const uint8_t* p, size_t left, TxLayout& L, std::vector<uint32_t>& in_off,
+                                std::vector<uint32_t>& out_off, uint64_t* excess) {
+  return tx_parse_impl(p, left, false, true, L, in_off, out_off, excess);
 }
 
 }  // namespace zg

@@ -31,6 +31,13 @@ EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
 HEADER_BYTES = 1487
 HDR_OK, HDR_MALFORMED, HDR_EQUIHASH, HDR_POW = 0, 1, 2, 3
 HDR_F_EQUIHASH, HDR_F_POW, HDR_F_REPEATED = 1, 2, 4
+# include/zg.h ZG_BLK_* (the first failing check of BlockVerifier::check) and ZG_BLK_F_* (every check that fails)
+(BLK_OK, BLK_MALFORMED, BLK_NONCANONICAL, BLK_EMPTY, BLK_COINBASE, BLK_SIZE, BLK_EXTRA_COINBASE, BLK_DUPLICATED,
+ BLK_SIGOPS, BLK_MERKLE_ROOT) = range(10)
+(BLK_F_EMPTY, BLK_F_COINBASE, BLK_F_SIZE, BLK_F_EXTRA_COINBASE, BLK_F_DUPLICATED, BLK_F_SIGOPS,
+ BLK_F_MERKLE_ROOT) = 1, 2, 4, 8, 16, 32, 64
+BLK_NO_INDEX = (1 << 64) - 1
+E_NOMEM = -5
 TREE_SPROUT, TREE_SAPLING = 0, 1     # include/zg.h ZG_TREE_*
 SPROUT_HEIGHT, SAPLING_HEIGHT = 29, 32   # storage/src/tree_state.rs H29 / H32
 E_TREE_FULL = -7
@@ -99,6 +106,11 @@ def lib():
         L.zg_tx_layout.argtypes = [u8p, sz, ctypes.POINTER(ctypes.c_uint64)]
         L.zg_sighash.argtypes = [vp, sz, u8p, ctypes.POINTER(ctypes.c_uint64), u32p, sz, u32p, u32p, u8p, u32p,
                                  ctypes.POINTER(ctypes.c_uint64), u32p, u8p, u8p, u8p]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.zg_block_layout.argtypes = [u8p, sz, u64p, u64p, sz]
+        L.zg_txids.argtypes = [vp, sz, u8p, u64p, u8p]
+        L.zg_blocks_verify.argtypes = [vp, sz, u8p, u64p, ctypes.c_uint64, ctypes.c_uint64, sz, u8p, u8p, u64p, u8p,
+                                       u64p, u8p]
         L.zg_last_sig_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.zg_equihash_verify.argtypes = [vp, ctypes.c_int, sz, u8p, sz, u8p, u8p, u8p]
         L.zg_headers_verify.argtypes = [vp, sz, u8p, ctypes.c_uint32, u8p, u8p, u8p]
@@ -285,6 +297,35 @@ def pack_sighash(txs, branch_ids, items):
     hashtype = (ctypes.c_uint32 * max(n, 1))(*[it[4] & 0xFFFFFFFF for it in items])
     return (b"".join(map(bytes, txs)), tx_off, branch, item_tx, index, b"".join(bytes(it[2]) for it in items),
             script_off, amount, hashtype)
+
+
+def block_layout(raw):
+    """zg_block_layout: Block::deserialize (chain/src/block.rs:10-14) over exactly these bytes -> (TX_* status,
+    [transactions, IndexedBlock::size, sigops, 1 when transaction 0 is a coinbase, index of the first later
+    coinbase or BLK_NO_INDEX, bytes consumed], the transactions' offsets); the list is zero and the offsets None
+    when the status is TX_MALFORMED. CPU, no context"""
+    out = (ctypes.c_uint64 * 6)()
+    buf = bytes(raw) + b"\0"
+    rc = lib().zg_block_layout(buf, len(raw), out, None, 0)
+    if rc < 0:
+        raise ZgError(rc, "zg_block_layout")
+    off = None
+    if rc != TX_MALFORMED:
+        tx_off = (ctypes.c_uint64 * (out[0] + 1))()
+        lib().zg_block_layout(buf, len(raw), out, tx_off, out[0] + 1)
+        off = list(tx_off)
+    return rc, list(out), off
+
+
+def pack_slices(slices):
+    """byte strings back to back -> (arena, their len + 1 offsets as ctypes)"""
+    off = (ctypes.c_uint64 * (len(slices) + 1))()
+    total = 0
+    for i, b in enumerate(slices):
+        off[i] = total
+        total += len(b)
+    off[len(slices)] = total
+    return b"".join(map(bytes, slices)), off
 
 
 def pow_valid(max_bits, bits, hash32):
@@ -534,6 +575,47 @@ class Context:
         self._chk(lib().zg_sighash(self._p, ntx, arena + b"\0", tx_off, branch, n, item_tx, index, scripts + b"\0",
                                    script_off, amount, hashtype, ts, hs, st))
         return list(ts.raw[:ntx]), [hs.raw[32 * i:32 * i + 32] for i in range(n)], list(st.raw[:n])
+
+    def txids(self, slices=None, arena=None, offsets=None):
+        """dhash256 of each byte string (IndexedTransaction::hash), ONE call -> 32-byte hashes in H256 storage
+        order. Either a list of byte strings, or one arena and the n + 1 offsets of its slices"""
+        if arena is None:
+            arena, off = pack_slices(slices)
+            n = len(slices)
+        else:
+            n = len(offsets) - 1
+            off = (ctypes.c_uint64 * (n + 1))(*offsets)
+        hs = ctypes.create_string_buffer(max(32 * n, 1))
+        self._chk(lib().zg_txids(self._p, n, bytes(arena) + b"\0", off, hs))
+        return [hs.raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def blocks_verify(self, blocks, max_block_size, max_block_sigops, txid_cap=None, want_ids=True):
+        """BlockVerifier::check (verification/src/verify_block.rs:31-40) over serialized blocks, ONE call ->
+        (statuses BLK_*, flags BLK_F_* masks, details, merkle roots, cumulative transaction counts, ids per
+        block). txid_cap: the capacity of the id buffer in transactions (default: sized by a first call when the
+        window needs more than the blocks' bytes allow for); a window that exceeds an explicit txid_cap raises
+        ZgError(E_NOMEM) whose `counts` holds the cumulative counts"""
+        n = len(blocks)
+        arena, off = pack_slices(blocks)
+        st = ctypes.create_string_buffer(max(n, 1))
+        fl = ctypes.create_string_buffer(max(n, 1))
+        det = (ctypes.c_uint64 * max(n, 1))()
+        roots = ctypes.create_string_buffer(max(32 * n, 1))
+        cnt = (ctypes.c_uint64 * (n + 1))()
+        cap = txid_cap if txid_cap is not None else len(arena) // 10 + 1   # no transaction is shorter than 10 bytes
+        ids = ctypes.create_string_buffer(max(32 * cap, 1)) if want_ids else None
+        rc = lib().zg_blocks_verify(self._p, n, arena + b"\0", off, max_block_size, max_block_sigops, cap, st, fl, det,
+                                    roots, cnt, ids)
+        if rc == E_NOMEM:
+            e = ZgError(rc, "blocks_verify: %d transactions, capacity %d" % (cnt[n], cap))
+            e.counts = list(cnt)
+            raise e
+        self._chk(rc)
+        counts = list(cnt)
+        per_block = [[ids.raw[32 * r:32 * r + 32] for r in range(counts[b], counts[b + 1])] for b in range(n)] \
+            if want_ids else None
+        return (list(st.raw[:n]), list(fl.raw[:n]), list(det)[:n], [roots.raw[32 * b:32 * b + 32] for b in range(n)],
+                counts, per_block)
 
     def last_sig_kernel_ms(self):
         """device time of the kernel(s) of the last ed25519_verify / ecdsa_verify / redjubjub_verify /
