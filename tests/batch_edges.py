@@ -23,7 +23,7 @@ MIX_SIZES = [3, 33]
 POOL = 257
 VARIANTS = 4                       # re-randomisations per source (Python G2 arithmetic on the host)
 RERAND_SEED = 0xED6E5
-K4_DEFAULT_MIN = 16384             # zebra_amd/csrc/zg.hip ZG_K4_MIN
+K4_DEFAULT_MIN = 16384             # zebra_amd/csrc/zg_host.h ZG_K4_MIN
 MAX_BATCH = 512
 
 

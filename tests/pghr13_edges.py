@@ -1,7 +1,7 @@
 """Case builders for the PGHR13 batch-check edge tests (tests/test_pghr13_edges.py on the CPU,
 tests/test_gpu_pghr13_edges.py on the GPU): ragged sizes under every launch shape of
 zg_pghr13_verify's batch path (zebra_amd/csrc/zg_pghr13.hip: k_pghr_straus<B>, k_pghr_bseg with K
-proofs per lane, the per-call chunk loop of zg.hip), one failing proof per call in the slots where a
+proofs per lane, the per-call chunk loop of zg_calls.hip), one failing proof per call in the slots where a
 lane map ends, slots the batch excludes, calls with nothing live.
 
 Every expectation here comes from the oracle alone: a slot's status is that of the C++ restatement of

@@ -2,272 +2,41 @@
 // One translation unit: the kernels (zg_kernels.h) are launched from here on the
 // context's private HIP stream. Everything that touches curve or field arithmetic runs
 // on the GPU; the host parses bytes, drives launches and the bisection, and moves data.
-#include <hip/hip_runtime.h>
-#include <errno.h>
 #include <stdlib.h>
-#include <string.h>
-#include <sys/random.h>
 
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../include/zg.h"
-#include "zg_blake2b.h"
-#include "zg_blocks.h"
+#include "zg_host.h"
 #include "zg_chacha.h"
-#include "zg_ecdsa.h"    // ZG_EC_COMB_*
-#include "zg_ed25519.h"  // ZG_ED_COMB_*
-#include "zg_jubjub.h"   // ZG_JJ_COMB_*
 #include "zg_kernels.h"
-#include "zg_msm.h"
-#include "zg_prep.h"
-#include "zg_sighash.h"
 #include "zg_vk_embed.h"  // generated from zebra_amd/res/*.json by zebra_amd/build.py
 
 using namespace zg;
 
 #define ZG_BLOCK 64
 #define ZG_NODE_CHUNK 4096
-#define ZG_LP_PARTS_MAX 8
 #define ZG_EV_SETTLE (15 + ZG_LP_PARTS_MAX)  // settle_batch's recompute (no timing)
-#define ZG_NEV (16 + ZG_LP_PARTS_MAX)  // [13]: zg_gt_check; [14..] line-product parts, [14 + max] chains done,
-                                       // [15 + max] settle_batch (no timing)
 // the pinned host block of a context: the root's 576-B Miller partial, the pipeline flags
 // (bfail, fused-wait failure), the K4 entry count, then the n statuses
 #define ZG_PIN_FLAGS 576
 #define ZG_PIN_ENTRIES 584
 #define ZG_PIN_STATUS 640
-#define ZG_NTIMINGS 9
-#define ZG_NSTATS 13
-#define ZG_TREE_COOP_BELOW 4096  // product-tree levels with fewer nodes run one wave per node
 #define ZG_LINE_PROD_MIN 32768   // shards from this many padded proofs run the f-chain as group line products
 #define ZG_QUAD_MIN 8192         // shards from this many (padded) proofs run the f-chain four proofs per lane (r02z: -4% at 16k, -1% at 8k)
-#define ZG_K4_MIN 16384          // lone batches from this many (padded) proofs sum r_i C_i by K4's Pippenger
-                                 // buckets; smaller lone batches by the GLV products in decode + the C tree
-                                 // levels (run_pipeline: batches in flight always use K4)
 #define ZG_LINES_LANE_MIN 32768  // straight-line R-chain from here (r03: 64k 14.93 -> 14.47 ms per batch in
                                  // flight; 16k 4.90 -> 5.14 and 8k 3.21 -> 3.63 favour the staged program)
-#define ZG_PGHR_CHUNK 65536      // proofs per batch check of zg_pghr13_verify (ZG_PGHR_CHUNK lowers it, 64 at the least)
-#define ZG_TXID_HOST_MIN 65536   // slices from this many bytes are hashed on host threads beside k_txid: a 100 KB
-                                 // transaction in a 65,536-transaction window, 15.5 -> 9.8 ms per call
 #define ZG_DEFAULT_PAIRS 8       // stream pairs per device (ZG_STREAM_PAIRS overrides, 1..16)
-#define ZG_HI_PAIRS 4            // high-priority stream pairs per device (zg_set_priority round-robin)
-
-namespace zg {  // zg_merkle.hip
-struct MerkleDev;
-MerkleDev* merkle_dev_new();
-void merkle_dev_free(MerkleDev* m);
-int merkle_combine(MerkleDev* m, hipStream_t st, int kind, size_t n, const uint8_t* l, const uint8_t* r,
-                   const uint8_t* depth, uint8_t* out, std::string* err);
-int merkle_empty_roots(MerkleDev* m, hipStream_t st, int kind, size_t levels, uint8_t* out, std::string* err);
-size_t merkle_state_max_bytes(int height);
-int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const uint8_t* state, size_t state_len,
-                      size_t n, const void* leaves, int leaves_on_device, size_t nmarks, const uint64_t* marks,
-                      uint8_t* roots, uint8_t* state_out, size_t* state_out_len, float* kernel_ms,
-                      void** arena, size_t* arena_cap, std::string* err);
-// zg_pghr13.hip
-struct BnDev;
-struct BnKey;
-BnDev* bn_dev_new();
-void bn_dev_free(BnDev* d);
-int bn_load_vk_json(BnDev* d, hipStream_t st, const char* json, size_t len, const BnKey** out, std::string* err);
-void bn_key_release(BnDev* d, const BnKey* k);
-void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* halves, int* p7_side);
-int bn_pghr13_verify(const BnKey* k, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
-                     const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
-                     uint8_t* status, float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap,
-                     std::string* err);
-int bn_pairing(hipStream_t st, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, std::string* err);
-}  // namespace zg
-
-// Per-device state shared by every context (batch slot) on that GPU: a FIXED pool of stream
-// pairs, created once, and the prepared verifying keys. A context only owns buffers, so a
-// process can hold any number of slots without creating another HIP stream / hardware queue.
-// Why: each hardware queue that dispatches a kernel with a private (scratch) segment keeps a
-// scratch allocation sized for the whole device; the process's scratch pool is bounded, and
-// with a stream pair per context the 7th in-flight context on one GPU pushed it over
-// (HSA_STATUS_ERROR_OUT_OF_RESOURCES from the queue). With the pool, the
-// number of queues -- hence of scratch reservations -- no longer grows with the slots.
-struct zg_dev {
-  int device = 0;
-  int ncu = 0;
-  int refs = 0;
-  std::mutex mu;  // the pool cursor and the VK cache
-  int npairs = 0;
-  hipStream_t main[16] = {}, side[16] = {};
-  // high-priority pairs (lazy, zg_set_priority): a few, so that concurrent checker contexts (one per
-  // verdict thread) do not serialise their final exponentiations on one stream
-  hipStream_t hi_main[ZG_HI_PAIRS] = {}, hi_side[ZG_HI_PAIRS] = {};
-  int hi_next = 0;
-  int next = 0;
-  struct VKEntry {
-    RawVK raw;
-    DevVK* d = nullptr;
-    uint32_t* comb = nullptr;  // the key's comb tables (ZG_COMB_POINTS x 96 B, k_vk_comb)
-    int err = 0;
-  };
-  std::vector<VKEntry*> vks;  // prepare_verifying_key once per distinct key per device
-  uint32_t* jj_comb = nullptr;  // Jubjub generators' comb tables (zg_jubjub.h), built on first use
-  uint32_t* ed_comb = nullptr;  // the Ed25519 base point's comb table (zg_ed25519.h), built on first use
-  uint32_t* ec_comb = nullptr;  // the secp256k1 generator's comb table (zg_ecdsa.h), built on first use
-  zg::MerkleDev* merkle = nullptr;  // Pedersen table + empty roots (zg_merkle.hip), first use
-  zg::BnDev* bn = nullptr;          // PGHR13 key, line and comb tables (zg_pghr13.hip), first use
-  std::atomic<int> inflight{0};     // contexts on this device with a batch begun and not finished
-};
 
 static std::mutex g_devs_mu;
 static zg_dev* g_devs[64] = {};
 static thread_local std::string g_create_err;
 
-struct zg_ctx {
-  int device = 0;
-  zg_dev* dev = nullptr;
-  hipStream_t stream = nullptr;  // from the device pool (not owned)
-  hipStream_t side = nullptr;    // VK-side root work, concurrent with the Miller kernels
-  int pair = 0;
-  std::mutex mu;
-  std::string err;
-  uint32_t cap = 0;  // power of two >= max_batch
-  int seeded = 0;
-  uint64_t seed = 0;
-  int vk_loaded[ZG_NKINDS] = {0, 0, 0};
-  int vk_iclen[ZG_NKINDS] = {0, 0, 0};
-  RawVK vk_raw[ZG_NKINDS];  // host copies of the loaded keys (shared alpha / beta / gamma test)
-  int merged = 0;           // loaded keys share alpha, beta, gamma: merged VK-side pairs (zg_batch.h)
-  DevVK* d_vk = nullptr;  // this slot's 3 kinds (copied from the device cache)
-  int* d_int = nullptr;   // scratch ints: [8] bfail, [9] fused-wait failure
-  // batch
-  uint8_t *d_proofs = nullptr, *d_kinds = nullptr, *d_inputs = nullptr, *d_ninputs = nullptr, *d_r = nullptr,
-          *d_status = nullptr, *d_bytes = nullptr, *d_okbits = nullptr;
-  G1A* d_ptA = nullptr;
-  G1A* d_ptAC = nullptr;
-  int* d_prog = nullptr;  // cap / 64: per lines block, steps published (fused R-chain + f-chain)
-  int ncu = 0;            // compute units of the device
-  int fuse = -1;          // ZG_LINES_FCHAIN: -1 auto (both grids resident at once), 0 never, 1 always
-  int fuse_off = 0;       // a fused launch ever timed out waiting: split launches from then on
-  int serial_side = 0;    // ZG_SERIAL_SIDE=1: the side-stream work runs on the main stream after the
-                          // product tree (measurement: the Miller kernels alone on the device)
-  G2A* d_ptB = nullptr;
-  Fq12* d_ftree = nullptr;
-  Fq2* d_lines = nullptr;  // cap x 68 x 3: per-proof line triples (R-chain -> f-chain)
-  Fq2* d_lprod = nullptr;  // cap / 4 x 68 x 6: per-group line products (k_line_prod)
-  Fq2* d_fstate = nullptr; // cap / 4 x 6: each group chain's f between its parts (k_batch_fchaing)
-  G1J* d_ctree = nullptr;
-  Fr* d_stree = nullptr;
-  MsmBufs msm = {};       // K4: Pippenger sum r_i C_i per key + root Fr sums (zg_msm.h)
-  int trees_built = 0;    // the full C / Fr trees exist for this batch (bisection only)
-  int c_tree_pending = 0; // the C tree is still being built on the side stream (ev[12])
-  // node checks
-  int* d_nodes = nullptr;
-  G1J* d_msm = nullptr;
-  Fq12* d_pairf = nullptr;
-  int* d_ok = nullptr;
-  Fq12* d_out = nullptr;
-  // state of the split API
-  int state = 0;
-  size_t n = 0, npad = 0;
-  const uint8_t* cur_ninputs = nullptr;  // device pointer or null
-  // this batch's inputs on the device: the context's own buffers (host-buffer calls copy into
-  // them), or the caller's HBM-resident buffers (zg_batch_begin_device: read in place, no copy)
-  const uint8_t *cur_proofs = nullptr, *cur_kinds = nullptr, *cur_inputs = nullptr;
-  int root_pairs_ready = 0;  // the pipeline already ran the root's MSM + VK pairs on `side`
-  int settled = 0;           // settle_batch ran for this batch
-  int alone_last = 0;        // the last batch ran with no other batch in flight (K4 shape)
-  int eager = 0;             // the pipeline's last steps copied the root partial, flags and statuses to h_pin (ev[4])
-  uint8_t* h_pin = nullptr;  // pinned host memory: ZG_PIN_* layout
-  uint8_t* h_gt = nullptr;   // pinned staging of zg_gt_check (partials in, verdict out; grow-only)
-  size_t h_gt_cap = 0;
-  int fused_last = 0;        // the last batch used the fused R-chain + f-chain launch
-  int lines_lane = -1;      // ZG_LINES_LANE: -1 auto (the straight-line R-chain from ZG_LINES_LANE_MIN padded
-                            // proofs, sized for 1 wave per SIMD when the batch is alone on the device, else
-                            // 2; the staged program below), 1 / 2 always straight-line sized for 2 / 1
-                            // waves per SIMD, 0 always the staged program (zg_kernels.h)
-  int quads = -1;            // ZG_FCHAIN_QUADS: -1 auto (npad >= ZG_QUAD_MIN), 0 never, 1 always (npad >= 4)
-  int line_group = -1;       // ZG_LINE_GROUP: proofs per group (k_line_prod): -1 auto (32 from ZG_LINE_PROD_MIN
-                             // padded proofs, else the quad chain), 0 never, a power of two >= 4 always
-  int lineprod_last = 0;     // the last batch's f-chain ran on group line products (no tree below the groups)
-  int lines_affine = 0;      // ZG_LINES_AFFINE: K (2, 4, 8) -- the group line products run on affine lines from
-                             // k_batch_lines_aff, K proofs per lane (round 6); 0 projective
-  int lines_affine_xl = 0;   // ZG_LINES_AFFINE_XL=1: its cross-lane variant (one inversion per wave; K = 4)
-  int affine_last = 0;       // the last batch's lines are affine (bisection re-forms projective ones)
-  int quad_split = 1;        // ZG_QUAD_SPLIT: 1 a step's four lines multiply first, then into f (Q4IK + GM / GMSQ,
-                             // round 6), 0 the fused Q4 / Q4SQ programs (same values)
-  int lp_parts = 0;          // ZG_LINE_PROD_PARTS: step parts overlapping line products and chains: 1..8 equal
-                             // parts, 0 (default) wave-aligned parts (lineprod_parts)
-  int glv_lds = ZG_DEC_GLV_LDS;  // ZG_DEC_GLV_LDS: decode's r_i A_i two columns per step from an LDS table, in a
-                             // launch of its own (K4 layout only; zg_decode.h)
-  int pairs_late = 0;        // ZG_PAIRS_LATE=1: with group line products, the root's VK MSM + pairs go on the side
-                             // stream AFTER the group chains instead of before them (round 6, r06f: 8k with line
-                             // products 2.88 -> 2.77 ms per batch, still behind the quad chain's 2.61; 16k 4.19 ->
-                             // 4.30, 64k 12.33 -> 12.46: not the default)
-  long k4_min = ZG_K4_MIN;   // ZG_K4_MIN overrides: K4 Pippenger from this many padded proofs, else decode GLV + C tree
-  int k4_last = 1;           // the last batch summed r_i C_i with K4 (0: the C tree is built, bisection reuses it)
-  int quads_last = 0;        // the last batch's f-chain ran four proofs per lane (no pair-level nodes)
-  int singles = -1;          // ZG_FCHAIN_SINGLE: -1 auto (a fused launch runs one proof per f-chain lane), 0 never
-  int singles_last = 0;      // the last batch's f-chain wrote the per-proof leaves (bisection reuses them)
-  size_t coop_below = ZG_TREE_COOP_BELOW;  // ZG_TREE_COOP_BELOW overrides (product-tree wave-per-node levels)
-  hipEvent_t ev[ZG_NEV] = {};
-  float timings[ZG_NTIMINGS] = {};
-  // [0] batches, [1] fused launches, [2] fused-wait failures, [3] B subgroup failures
-  // (bfail, deferred recomputes), [4] bisections, [5] nodes checked by bisection,
-  // [6] K4 bucket entries of the last batch (points with a non-zero digit, summed over windows)
-  uint64_t stats[ZG_NSTATS] = {};
-  uint64_t calls = 0;
-  int debug_each = 0;         // ZG_DEBUG_EACH=1: every batch's statuses re-checked per proof
-  uint8_t* d_dbg = nullptr;   // the per-proof statuses of that re-check
-  const zg::BnKey* bn_key = nullptr;  // this slot's PGHR13 key (an immutable, reference-counted entry of the device cache)
-  uint8_t* prep_arena = nullptr;  // zg_prep_batch device buffers (grow-only)
-  size_t prep_arena_cap = 0;
-  void* tree_arena = nullptr;  // zg_tree_roots scratch (grow-only, zg_merkle.hip)
-  size_t tree_arena_cap = 0;
-  void* bn_arena = nullptr;  // zg_pghr13_verify scratch (grow-only, zg_pghr13.hip)
-  size_t bn_arena_cap = 0;
-  // the launch shape of zg_pghr13_verify's batch check (zg_pghr13.hip bn_pghr13_shape; zg_pghr13_shape reports it)
-  int pghr_straus_b = 0;     // ZG_STRAUS_B: proofs per lane of k_pghr_straus, 1 / 2 / 4; 0 (any other value) by size
-  int pghr_bseg_k = 0;       // ZG_BSEG_K: proofs per lane of k_pghr_bseg, 1..32 (larger: 32); 0 (or less) by size
-  size_t pghr_chunk = ZG_PGHR_CHUNK;  // ZG_PGHR_CHUNK: proofs per batch check of one call, 64..65,536
-  size_t txid_host_min = ZG_TXID_HOST_MIN;  // ZG_TXID_HOST_MIN: slices of at least this many bytes are hashed on
-                                            // host threads beside k_txid; 0: never
-  hipEvent_t sig_ev[2] = {};  // around the kernel of the last signature call (zg_last_sig_kernel_ms), first use
-  float sig_ms = 0.0f;
-};
-
-static int fail(zg_ctx* c, int code, const std::string& msg) {
-  c->err = msg;
-  return code;
-}
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(ctx, ZG_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
-// Wait for an event by polling (hipEventQuery + a short sleep) instead of hipEventSynchronize /
-// hipStreamSynchronize: the host loop of batches in flight calls into the runtime from two threads
-// (batch launches / harvests on the main one, the verdicts' final exponentiations on a worker), and
-// a blocking synchronize on one thread held up the other's calls until the GPU work it waited for
-// had finished (8k shards: every relaunch came ~1 ms after the verdict's final exponentiation).
-static hipError_t wait_event(hipEvent_t e) {
-  for (;;) {
-    const hipError_t r = hipEventQuery(e);
-    if (r != hipErrorNotReady) return r;
-    std::this_thread::sleep_for(std::chrono::microseconds(10));
-  }
-}
-
 static unsigned nblocks(size_t n) { return (unsigned)((n + ZG_BLOCK - 1) / ZG_BLOCK); }
 
 extern "C" const char* zg_last_error(zg_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
+// a buffer of the context: its owner frees it (zg_destroy)
 template <class T>
-static hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, sizeof(T) * (count ? count : 1));
+static hipError_t dalloc(zg_ctx* ctx, T** p, size_t count) {
+  return ctx->own.alloc(p, sizeof(T) * (count ? count : 1));
 }
 
 static void dev_release(zg_dev* d) {
@@ -386,44 +155,44 @@ extern "C" zg_ctx* zg_create(const zg_config* cfg) {
   auto A = [&](hipError_t r) {
     if (e == hipSuccess) e = r;
   };
-  A(dalloc(&ctx->d_vk, ZG_NKINDS));
-  A(dalloc(&ctx->d_int, 16));
-  A(dalloc(&ctx->d_proofs, (size_t)cap * 192));
-  A(dalloc(&ctx->d_kinds, cap));
-  A(dalloc(&ctx->d_inputs, (size_t)cap * 288));
-  A(dalloc(&ctx->d_ninputs, cap));
-  A(dalloc(&ctx->d_r, ((size_t)cap + 3) / 4 * 64));  // whole ChaCha20 blocks
-  A(dalloc(&ctx->d_status, cap));
-  A(dalloc(&ctx->d_okbits, (size_t)cap * 3));
-  A(dalloc(&ctx->d_bytes, (size_t)576 * ZG_NODE_CHUNK));
-  A(dalloc(&ctx->d_ptA, cap));
-  A(dalloc(&ctx->d_ptAC, 2 * (size_t)cap));
-  A(dalloc(&ctx->d_prog, (size_t)cap / 64 + 1));
-  A(dalloc(&ctx->d_ptB, cap));
-  A(dalloc(&ctx->d_ftree, 2 * (size_t)cap));
-  A(dalloc(&ctx->d_lines, (size_t)cap * ZG_NCOEFF * 3));
+  A(dalloc(ctx, &ctx->d_vk, ZG_NKINDS));
+  A(dalloc(ctx, &ctx->d_int, 16));
+  A(dalloc(ctx, &ctx->d_proofs, (size_t)cap * 192));
+  A(dalloc(ctx, &ctx->d_kinds, cap));
+  A(dalloc(ctx, &ctx->d_inputs, (size_t)cap * 288));
+  A(dalloc(ctx, &ctx->d_ninputs, cap));
+  A(dalloc(ctx, &ctx->d_r, ((size_t)cap + 3) / 4 * 64));  // whole ChaCha20 blocks
+  A(dalloc(ctx, &ctx->d_status, cap));
+  A(dalloc(ctx, &ctx->d_okbits, (size_t)cap * 3));
+  A(dalloc(ctx, &ctx->d_bytes, (size_t)576 * ZG_NODE_CHUNK));
+  A(dalloc(ctx, &ctx->d_ptA, cap));
+  A(dalloc(ctx, &ctx->d_ptAC, 2 * (size_t)cap));
+  A(dalloc(ctx, &ctx->d_prog, (size_t)cap / 64 + 1));
+  A(dalloc(ctx, &ctx->d_ptB, cap));
+  A(dalloc(ctx, &ctx->d_ftree, 2 * (size_t)cap));
+  A(dalloc(ctx, &ctx->d_lines, (size_t)cap * ZG_NCOEFF * 3));
   // group line products: sized for the smallest group that can run on this context (an explicit
   // ZG_LINE_GROUP, else the automatic 32 from ZG_LINE_PROD_MIN padded proofs; none below that)
   const uint32_t lp_gmin = ctx->line_group > 0 ? (uint32_t)ctx->line_group
                                                 : ctx->line_group < 0 && cap >= ZG_LINE_PROD_MIN ? 32u : 0u;
-  if (lp_gmin) A(dalloc(&ctx->d_lprod, ((size_t)cap / lp_gmin + 1) * ZG_NCOEFF * 6));
-  if (lp_gmin) A(dalloc(&ctx->d_fstate, ((size_t)cap / lp_gmin + 1) * 6));
-  A(dalloc(&ctx->d_ctree, 2 * (size_t)cap * ZG_NKINDS));
-  A(dalloc(&ctx->d_stree, 2 * (size_t)cap * ZG_NKINDS * ZG_MAX_IC));
-  A(dalloc(&ctx->msm.count, ZG_MSM_NCOUNT_MAX));
-  A(dalloc(&ctx->msm.start, ZG_MSM_NCOUNT_MAX + 1));
-  A(dalloc(&ctx->msm.cursor, ZG_MSM_NCOUNT_MAX));
-  A(dalloc(&ctx->msm.entries, 2 * (size_t)cap * ZG_MSM_WMAX));
-  A(dalloc(&ctx->msm.cd, (size_t)cap * ZG_MSM_CD));
-  A(dalloc(&ctx->msm.seg, (size_t)ZG_MSM_GROUPS_MAX * ZG_MSM_SEG_MAX * 2));
-  A(dalloc(&ctx->msm.wsum, ZG_MSM_GROUPS_MAX));
-  A(dalloc(&ctx->msm.frpart, ((size_t)cap / ZG_FR_CHUNK + 1) * ZG_NKINDS * ZG_MAX_IC));
-  A(dalloc(&ctx->d_nodes, ZG_NODE_CHUNK));
-  A(dalloc(&ctx->d_msm, (size_t)ZG_NODE_CHUNK * ZG_NKINDS * ZG_MSM_SLOTS * ZG_SHIFTS));
-  A(dalloc(&ctx->d_pairf, (size_t)ZG_NODE_CHUNK * ZG_NODE_PAIRS));
-  A(dalloc(&ctx->d_ok, ZG_NODE_CHUNK));
-  A(dalloc(&ctx->d_out, ZG_NODE_CHUNK));
-  if (ctx->debug_each) A(dalloc(&ctx->d_dbg, cap));
+  if (lp_gmin) A(dalloc(ctx, &ctx->d_lprod, ((size_t)cap / lp_gmin + 1) * ZG_NCOEFF * 6));
+  if (lp_gmin) A(dalloc(ctx, &ctx->d_fstate, ((size_t)cap / lp_gmin + 1) * 6));
+  A(dalloc(ctx, &ctx->d_ctree, 2 * (size_t)cap * ZG_NKINDS));
+  A(dalloc(ctx, &ctx->d_stree, 2 * (size_t)cap * ZG_NKINDS * ZG_MAX_IC));
+  A(dalloc(ctx, &ctx->msm.count, ZG_MSM_NCOUNT_MAX));
+  A(dalloc(ctx, &ctx->msm.start, ZG_MSM_NCOUNT_MAX + 1));
+  A(dalloc(ctx, &ctx->msm.cursor, ZG_MSM_NCOUNT_MAX));
+  A(dalloc(ctx, &ctx->msm.entries, 2 * (size_t)cap * ZG_MSM_WMAX));
+  A(dalloc(ctx, &ctx->msm.cd, (size_t)cap * ZG_MSM_CD));
+  A(dalloc(ctx, &ctx->msm.seg, (size_t)ZG_MSM_GROUPS_MAX * ZG_MSM_SEG_MAX * 2));
+  A(dalloc(ctx, &ctx->msm.wsum, ZG_MSM_GROUPS_MAX));
+  A(dalloc(ctx, &ctx->msm.frpart, ((size_t)cap / ZG_FR_CHUNK + 1) * ZG_NKINDS * ZG_MAX_IC));
+  A(dalloc(ctx, &ctx->d_nodes, ZG_NODE_CHUNK));
+  A(dalloc(ctx, &ctx->d_msm, (size_t)ZG_NODE_CHUNK * ZG_NKINDS * ZG_MSM_SLOTS * ZG_SHIFTS));
+  A(dalloc(ctx, &ctx->d_pairf, (size_t)ZG_NODE_CHUNK * ZG_NODE_PAIRS));
+  A(dalloc(ctx, &ctx->d_ok, ZG_NODE_CHUNK));
+  A(dalloc(ctx, &ctx->d_out, ZG_NODE_CHUNK));
+  if (ctx->debug_each) A(dalloc(ctx, &ctx->d_dbg, cap));
   A(hipHostMalloc((void**)&ctx->h_pin, ZG_PIN_STATUS + (size_t)cap, hipHostMallocDefault));
   for (int i = 0; i < ZG_NEV; i++)
     A(i < 14 ? hipEventCreate(&ctx->ev[i]) : hipEventCreateWithFlags(&ctx->ev[i], hipEventDisableTiming));
@@ -451,14 +220,6 @@ extern "C" void zg_destroy(zg_ctx* ctx) {
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   if (ctx->side) hipStreamSynchronize(ctx->side);
   if (ctx->bn_key && ctx->dev) zg::bn_key_release(ctx->dev->bn, ctx->bn_key);
-  void* ptrs[] = {ctx->d_vk, ctx->d_int, ctx->d_proofs, ctx->d_kinds, ctx->d_inputs, ctx->d_ninputs,
-                  ctx->d_r, ctx->d_status, ctx->d_bytes, ctx->d_ptA, ctx->d_ptB, ctx->d_ftree, ctx->d_ctree,
-                  ctx->d_stree, ctx->d_nodes, ctx->d_msm, ctx->d_pairf, ctx->d_ok, ctx->d_out, ctx->d_lines, ctx->d_lprod, ctx->d_fstate,
-                  ctx->d_okbits, ctx->d_ptAC, ctx->d_prog, ctx->msm.count, ctx->msm.start, ctx->msm.cursor,
-                  ctx->msm.entries, ctx->msm.cd, ctx->msm.seg, ctx->msm.wsum, ctx->msm.frpart, ctx->tree_arena,
-                  ctx->bn_arena, ctx->d_dbg, ctx->prep_arena};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
   if (ctx->h_pin) hipHostFree(ctx->h_pin);
   if (ctx->h_gt) hipHostFree(ctx->h_gt);
   for (int i = 0; i < ZG_NEV; i++)
@@ -467,7 +228,7 @@ extern "C" void zg_destroy(zg_ctx* ctx) {
     if (e) hipEventDestroy(e);
   set_state(ctx, 0);
   zg_dev* d = ctx->dev;
-  delete ctx;
+  delete ctx;  // its device buffers and arenas go with their owners (zg_ctx::own, the DevArenas)
   if (d) dev_release(d);
 }
 
@@ -688,8 +449,9 @@ extern "C" int zg_verify_each(zg_ctx* ctx, size_t n, const uint8_t* proofs, cons
   for (size_t i = 0; i < n; i++)
     if (kinds[i] >= ZG_NKINDS || !ctx->vk_loaded[kinds[i]]) return fail(ctx, ZG_E_NOVK, "verifying key not loaded");
   if (!n) return ZG_OK;
+  DevScratch s;
   uint8_t* d_gts = nullptr;
-  if (gts) HIPCHK(hipMalloc(&d_gts, 576 * n));
+  if (gts) HIPCHK(s.alloc(&d_gts, 576 * n));
   HIPCHK(hipMemcpyAsync(ctx->d_proofs, proofs, 192 * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_kinds, kinds, n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_inputs, inputs, 288 * n, hipMemcpyHostToDevice, ctx->stream));
@@ -701,7 +463,6 @@ extern "C" int zg_verify_each(zg_ctx* ctx, size_t n, const uint8_t* proofs, cons
   if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->d_status, n, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && gts) e = hipMemcpyAsync(gts, d_gts, 576 * n, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (d_gts) hipFree(d_gts);
   if (e != hipSuccess) return fail(ctx, ZG_E_HIP, std::string("zg_verify_each: ") + hipGetErrorString(e));
   return ZG_OK;
 }
@@ -710,32 +471,9 @@ extern "C" int zg_verify_each(zg_ctx* ctx, size_t n, const uint8_t* proofs, cons
 static void gen_scalars(zg_ctx* ctx, size_t n, std::vector<uint8_t>& r) {
   r.resize(n * 16);
   if (ctx->seeded) {
-    for (size_t i = 0; i < n; i++) {
-      Blake2b h(16);
-      h.update("zg-batch-r", 10);
-      uint8_t le[8];
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)(ctx->seed >> (8 * b));
-      h.update(le, 8);
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)((uint64_t)i >> (8 * b));
-      h.update(le, 8);
-      h.final(&r[16 * i]);
-    }
+    for (size_t i = 0; i < n; i++) seeded_bytes("zg-batch-r", ctx->seed, i, &r[16 * i], 16);
   }
   // any 16 bytes are a valid batch scalar: r_i = (2a + 1) + b lambda != 0 (zg_groth16.h)
-}
-
-static bool os_random(void* buf, size_t len) {
-  uint8_t* p = (uint8_t*)buf;
-  size_t off = 0;
-  while (off < len) {
-    ssize_t got = getrandom(p + off, len - off, 0);
-    if (got < 0) {
-      if (errno == EINTR) continue;
-      return false;
-    }
-    off += (size_t)got;
-  }
-  return true;
 }
 
 // r_i of the current batch into d_r. Seeded contexts (tests) derive them on the host
@@ -814,34 +552,6 @@ hipError_t launch_prog_fchaing(hipStream_t st, const BatchBufs& b, const Fq2* lp
 hipError_t launch_prog_lines_fchain(unsigned blocks, hipStream_t st, const BatchBufs& b, Fq2* lines, int* prog,
                                     int* fail, int per);
 hipError_t launch_prog_fchain1(unsigned blocks, hipStream_t st, const BatchBufs& b, const Fq2* lines, const int* gate);
-hipError_t launch_jj_comb(hipStream_t st, uint32_t* table);                                    // zg_jubjub.hip
-hipError_t launch_redjubjub(hipStream_t st, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                            const uint8_t* gen, int n, const uint32_t* comb, uint8_t* ok);
-hipError_t launch_jj_decode(hipStream_t st, const uint8_t* pts, int n, uint8_t* status, uint8_t* xy);
-hipError_t launch_ed_comb(hipStream_t st, uint32_t* table);                                    // zg_ed25519.hip
-hipError_t launch_ec_comb(hipStream_t st, uint32_t* table);                                    // zg_ecdsa.hip
-hipError_t launch_ecdsa(hipStream_t st, const uint8_t* pubkeys, const uint8_t* pubkey_len, const uint8_t* sigs,
-                        const uint32_t* sig_off, const uint8_t* msg, int n, const uint32_t* comb, uint8_t* status);
-hipError_t launch_ed25519(hipStream_t st, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg, int n,
-                          const uint32_t* comb, uint8_t* status);
-hipError_t launch_sighash_digests(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
-                                  const uint32_t* out_off, const uint32_t* jobs, int njobs, uint8_t* digests);  // zg_sighash.hip
-hipError_t launch_sighash_items(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
-                                const uint32_t* out_off, const uint8_t* digests, const uint8_t* scripts,
-                                const ShDevItem* items, int n, uint8_t* hashes);
-hipError_t launch_txid(hipStream_t st, const uint8_t* arena, const TxidSlice* slices, int n, uint8_t* out);  // zg_blocks.hip
-hipError_t launch_block_merkle(hipStream_t st, const uint8_t* arena, const MerkleBlk* blks, int nblk,
-                               const uint8_t* ids, uint8_t* ping, uint8_t* pong, uint8_t* roots, uint8_t* match);
-int equihash_solution_bytes(int params);                                                      // zg_equihash.hip
-hipError_t launch_equihash(hipStream_t st, int params, const uint8_t* inputs, size_t in_stride, int in_len,
-                           const uint8_t* sols, size_t sol_stride, int n, uint8_t* ok, uint8_t* repeated);
-hipError_t launch_headers(hipStream_t st, const uint8_t* headers, int n, uint32_t max_bits, uint8_t* eq_ok,
-                          uint8_t* eq_rep, uint8_t* status, uint8_t* hashes, uint8_t* flags);
-hipError_t launch_prep_sapling(hipStream_t st, const uint8_t* kinds, const uint8_t* fields, int n, uint8_t* inputs,
-                               uint8_t* codes);
-hipError_t launch_sapling_bvk(hipStream_t st, int ntx, const uint32_t* off, const uint32_t* nspends,
-                              const uint8_t* cvs, const int64_t* vb, const uint32_t* comb, uint8_t* bvk,
-                              uint8_t* status);
 }
 
 // The pipeline on device-resident inputs already in ctx buffers.
@@ -1549,670 +1259,6 @@ extern "C" int zg_stats(zg_ctx* ctx, uint64_t* out, size_t n) {
   return ZG_OK;
 }
 
-// ------------------------------------------------------------------ signature and header calls: shared pieces
-// a fixed-base comb table of the device (*slot, a member of zg_dev), built on first use by `launch`
-static int comb_table(zg_ctx* ctx, uint32_t** slot, size_t bytes, hipError_t (*launch)(hipStream_t, uint32_t*),
-                      const char* what, const uint32_t** out) {
-  std::lock_guard<std::mutex> g(ctx->dev->mu);
-  if (!*slot) {
-    uint32_t* t = nullptr;
-    HIPCHK(hipMalloc(&t, bytes));
-    hipError_t e = launch(ctx->stream, t);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      hipFree(t);
-      return fail(ctx, ZG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    }
-    *slot = t;
-  }
-  *out = *slot;
-  return ZG_OK;
-}
-
-// The two events around a call's kernels (created on first use): sig_timed brackets the launch, sig_sync
-// waits for the stream after the copies back and keeps the kernel time for zg_last_sig_kernel_ms
-template <class Launch>
-static hipError_t sig_timed(zg_ctx* ctx, Launch launch) {
-  for (hipEvent_t& e : ctx->sig_ev)
-    if (!e) {
-      const hipError_t r = hipEventCreate(&e);
-      if (r != hipSuccess) return r;
-    }
-  hipError_t r = hipEventRecord(ctx->sig_ev[0], ctx->stream);
-  if (r == hipSuccess) r = launch();
-  if (r == hipSuccess) r = hipEventRecord(ctx->sig_ev[1], ctx->stream);
-  return r;
-}
-static hipError_t sig_sync(zg_ctx* ctx) {
-  const hipError_t r = hipStreamSynchronize(ctx->stream);
-  if (r == hipSuccess) hipEventElapsedTime(&ctx->sig_ms, ctx->sig_ev[0], ctx->sig_ev[1]);
-  return r;
-}
-
-// device buffers of one call, freed on every path
-struct DevScratch {
-  std::vector<void*> p;
-  ~DevScratch() {
-    for (void* q : p) hipFree(q);
-  }
-  template <class T>
-  hipError_t alloc(T** x, size_t bytes) {
-    hipError_t e = hipMalloc((void**)x, bytes ? bytes : 1);
-    if (e == hipSuccess) p.push_back(*x);
-    return e;
-  }
-};
-
-extern "C" int zg_last_sig_kernel_ms(zg_ctx* ctx, float* ms) {
-  if (!ctx || !ms) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  *ms = ctx->sig_ms;
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ Sapling signatures (zg_jubjub.h)
-extern "C" int zg_redjubjub_verify(zg_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                                   const uint8_t* gen, uint8_t* ok) {
-  if (!ctx || (n && (!vk || !sig || !msg || !gen || !ok)) || n > (1u << 30)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint32_t* comb = nullptr;
-  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
-                      "Jubjub comb tables", &comb);
-  if (rc) return rc;
-  DevScratch s;
-  uint8_t *dvk, *dsig, *dmsg, *dgen, *dok;
-  HIPCHK(s.alloc(&dvk, 32 * n));
-  HIPCHK(s.alloc(&dsig, 64 * n));
-  HIPCHK(s.alloc(&dmsg, 64 * n));
-  HIPCHK(s.alloc(&dgen, n));
-  HIPCHK(s.alloc(&dok, n));
-  HIPCHK(hipMemcpyAsync(dvk, vk, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dmsg, msg, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dgen, gen, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] { return launch_redjubjub(ctx->stream, dvk, dsig, dmsg, dgen, (int)n, comb, dok); }));
-  HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ JoinSplit signatures (zg_ed25519.h)
-extern "C" int zg_ed25519_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkey, const uint8_t* sig, const uint8_t* msg,
-                                 uint8_t* status) {
-  if (!ctx || (n && (!pubkey || !sig || !msg || !status)) || n > (1u << 30)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint32_t* comb = nullptr;
-  int rc = comb_table(ctx, &ctx->dev->ed_comb, sizeof(uint32_t) * ZG_ED_COMB_WORDS * ZG_ED_COMB_POINTS, launch_ed_comb,
-                      "Ed25519 comb table", &comb);
-  if (rc) return rc;
-  DevScratch s;
-  uint8_t *dpk, *dsig, *dmsg, *dst;
-  HIPCHK(s.alloc(&dpk, 32 * n));
-  HIPCHK(s.alloc(&dsig, 64 * n));
-  HIPCHK(s.alloc(&dmsg, 32 * n));
-  HIPCHK(s.alloc(&dst, n));
-  HIPCHK(hipMemcpyAsync(dpk, pubkey, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dsig, sig, 64 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] { return launch_ed25519(ctx->stream, dpk, dsig, dmsg, (int)n, comb, dst); }));
-  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ transparent input signatures (zg_ecdsa.h)
-extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, const uint8_t* pubkey_len,
-                               const uint8_t* sigs, const uint32_t* sig_off, const uint8_t* msg, uint8_t* status) {
-  if (!ctx || (n && (!pubkeys || !pubkey_len || !sigs || !sig_off || !msg || !status)) || n > (1u << 30))
-    return ZG_E_INVAL;
-  for (size_t i = 0; i < n; i++)  // a lane reads sigs[sig_off[i] .. sig_off[i+1]) of a buffer of sig_off[n] bytes
-    if (sig_off[i + 1] < sig_off[i]) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint32_t* comb = nullptr;
-  int rc = comb_table(ctx, &ctx->dev->ec_comb, sizeof(uint32_t) * ZG_EC_COMB_WORDS * ZG_EC_COMB_POINTS, launch_ec_comb,
-                      "secp256k1 comb table", &comb);
-  if (rc) return rc;
-  const size_t sig_bytes = (size_t)sig_off[n] - sig_off[0];
-  DevScratch s;
-  uint8_t *dpk, *dlen, *dsig, *dmsg, *dst;
-  uint32_t* doff;
-  HIPCHK(s.alloc(&dpk, ZG_ECDSA_PUBKEY_STRIDE * n));
-  HIPCHK(s.alloc(&dlen, n));
-  HIPCHK(s.alloc(&dsig, sig_bytes ? sig_bytes : 1));
-  HIPCHK(s.alloc(&doff, sizeof(uint32_t) * (n + 1)));
-  HIPCHK(s.alloc(&dmsg, 32 * n));
-  HIPCHK(s.alloc(&dst, n));
-  HIPCHK(hipMemcpyAsync(dpk, pubkeys, ZG_ECDSA_PUBKEY_STRIDE * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dlen, pubkey_len, n, hipMemcpyHostToDevice, ctx->stream));
-  if (sig_bytes) HIPCHK(hipMemcpyAsync(dsig, sigs + sig_off[0], sig_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(doff, sig_off, sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dmsg, msg, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  // the device buffer starts at sig_off[0]: the kernel subtracts it
-  HIPCHK(sig_timed(ctx, [&] { return launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, dmsg, (int)n, comb, dst); }));
-  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ signature hashes (zg_sighash.h)
-extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
-                          const uint32_t* tx_branch_id, size_t n, const uint32_t* item_tx, const uint32_t* input_index,
-                          const uint8_t* scripts, const uint32_t* script_off, const uint64_t* amount,
-                          const uint32_t* hashtype, uint8_t* tx_status, uint8_t* hashes, uint8_t* status) {
-  if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status)) ||
-      (n && (!item_tx || !input_index || !scripts || !script_off || !amount || !hashtype || !hashes || !status)) ||
-      ntx > (1u << 30) || n > (1u << 30))
-    return ZG_E_INVAL;
-  for (size_t t = 0; t < ntx; t++)
-    if (tx_off[t + 1] < tx_off[t]) return ZG_E_INVAL;
-  if (ntx && tx_off[ntx] - tx_off[0] > (1ull << 31)) return ZG_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (script_off[i + 1] < script_off[i] || item_tx[i] >= ntx) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!ntx && !n) return ZG_OK;
-
-  // the layouts: every offset a lane follows is checked here
-  const uint64_t base0 = ntx ? tx_off[0] : 0;
-  std::vector<ShDevTx> dtx(ntx ? ntx : 1);
-  std::vector<uint32_t> in_off, out_off;
-  for (size_t t = 0; t < ntx; t++) {
-    ShDevTx& d = dtx[t];
-    tx_status[t] = (uint8_t)tx_parse(txs + tx_off[t], (size_t)(tx_off[t + 1] - tx_off[t]), d.L, in_off, out_off);
-    d.base = (uint32_t)(tx_off[t] - base0);
-    d.branch_id = tx_branch_id[t];
-    d.dig = 0;
-  }
-  // the items a lane takes, and the digests they read
-  std::vector<ShDevItem> items;
-  std::vector<uint64_t> cost;
-  std::vector<uint8_t> need(ntx ? ntx : 1, 0);
-  items.reserve(n);
-  for (size_t i = 0; i < n; i++) {
-    const ShDevTx& d = dtx[item_tx[i]];
-    const TxLayout& L = d.L;
-    const uint8_t ts = tx_status[item_tx[i]];
-    memset(hashes + 32 * i, 0, 32);
-    status[i] = ts == ZG_TX_MALFORMED ? ZG_SIGHASH_TX_MALFORMED : ts == ZG_TX_NONCANONICAL ? ZG_SIGHASH_TX_NONCANONICAL
-              : L.sigver && input_index[i] != ZG_SIGHASH_NO_INPUT && input_index[i] >= L.n_in ? ZG_SIGHASH_INPUT_RANGE
-                                                                                             : ZG_SIGHASH_OK;
-    if (status[i] != ZG_SIGHASH_OK) continue;
-    const uint32_t base = sh_base(hashtype[i]), acp = hashtype[i] & 0x80;
-    const uint32_t slen = script_off[i + 1] - script_off[i];
-    if (!L.sigver && input_index[i] >= L.n_in && (acp || base == SH_SINGLE)) continue;  // the zero hash, OK
-    items.push_back(ShDevItem{item_tx[i], input_index[i], script_off[i] - script_off[0], slen, hashtype[i], (uint32_t)i,
-                              amount[i]});
-    if (L.sigver) {
-      need[item_tx[i]] |= (uint8_t)((acp ? 0 : 1 << SH_PREVOUTS) | (!acp && base == SH_ALL ? 1 << SH_SEQUENCES : 0) |
-                                    (base == SH_ALL ? 1 << SH_OUTPUTS : 0) | (L.n_js ? 1 << SH_JOINSPLITS : 0) |
-                                    (L.sigver == 2 && L.n_spend ? 1 << SH_SPENDS : 0) |
-                                    (L.sigver == 2 && L.n_sout ? 1 << SH_SOUTPUTS : 0));
-      cost.push_back(2 * (uint64_t)(512 + slen));  // a BLAKE2b compression per 128 bytes, about two SHA-256 ones
-    } else {
-      cost.push_back(acp ? 256 + (uint64_t)slen + L.consumed - L.lock_off : (uint64_t)L.consumed + slen);
-    }
-  }
-  std::vector<uint32_t> order(items.size());
-  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-  std::vector<ShDevItem> sorted(items.size() ? items.size() : 1);
-  for (size_t k = 0; k < order.size(); k++) sorted[k] = items[order[k]];
-  std::vector<uint32_t> jobs;
-  uint32_t ndig = 0;
-  for (size_t t = 0; t < ntx; t++)
-    if (need[t]) {
-      dtx[t].dig = ndig++;
-      for (int w = 0; w < SH_DIGESTS; w++)
-        if (need[t] >> w & 1) jobs.push_back((uint32_t)(t << 3) | (uint32_t)w);
-    }
-  const size_t m = items.size();
-  if (!m) return ZG_OK;
-
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0), script_bytes = (size_t)script_off[n] - script_off[0];
-  DevScratch s;
-  uint8_t *darena, *dscripts, *ddig, *dhash;
-  ShDevTx* dtxs;
-  ShDevItem* ditems;
-  uint32_t *din, *dout, *djobs;
-  HIPCHK(s.alloc(&darena, arena_bytes + 8));
-  HIPCHK(s.alloc(&dscripts, script_bytes + 8));
-  HIPCHK(s.alloc(&ddig, (size_t)32 * SH_DIGESTS * (ndig ? ndig : 1)));
-  HIPCHK(s.alloc(&dhash, 32 * m));
-  HIPCHK(s.alloc(&dtxs, sizeof(ShDevTx) * ntx));
-  HIPCHK(s.alloc(&ditems, sizeof(ShDevItem) * m));
-  HIPCHK(s.alloc(&din, sizeof(uint32_t) * (in_off.size() + 1)));
-  HIPCHK(s.alloc(&dout, sizeof(uint32_t) * (out_off.size() + 1)));
-  HIPCHK(s.alloc(&djobs, sizeof(uint32_t) * (jobs.size() + 1)));
-  HIPCHK(hipMemcpyAsync(darena, txs + base0, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (script_bytes)
-    HIPCHK(hipMemcpyAsync(dscripts, scripts + script_off[0], script_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dtxs, dtx.data(), sizeof(ShDevTx) * ntx, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ditems, sorted.data(), sizeof(ShDevItem) * m, hipMemcpyHostToDevice, ctx->stream));
-  if (!in_off.empty())
-    HIPCHK(hipMemcpyAsync(din, in_off.data(), sizeof(uint32_t) * in_off.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (!out_off.empty())
-    HIPCHK(hipMemcpyAsync(dout, out_off.data(), sizeof(uint32_t) * out_off.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (!jobs.empty())
-    HIPCHK(hipMemcpyAsync(djobs, jobs.data(), sizeof(uint32_t) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] {
-    const hipError_t e = launch_sighash_digests(ctx->stream, darena, dtxs, din, dout, djobs, (int)jobs.size(), ddig);
-    if (e != hipSuccess) return e;
-    return launch_sighash_items(ctx->stream, darena, dtxs, din, dout, ddig, dscripts, ditems, (int)m, dhash);
-  }));
-  std::vector<uint8_t> hh(32 * m);
-  HIPCHK(hipMemcpyAsync(hh.data(), dhash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * sorted[k].slot, hh.data() + 32 * k, 32);
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ block bodies (zg_blocks.h)
-// The slices of one call: the kernel's, longest first (a wave's lanes then run similar lengths and the
-// longest chains start first), and those of at least ZG_TXID_HOST_MIN bytes, which host threads hash beside it
-struct TxidPlan {
-  std::vector<TxidSlice> dev, host;
-};
-static void txid_plan(const zg_ctx* ctx, const std::vector<TxidSlice>& all, TxidPlan& P) {
-  for (const TxidSlice& s : all) (ctx->txid_host_min && s.len >= ctx->txid_host_min ? P.host : P.dev).push_back(s);
-  std::stable_sort(P.dev.begin(), P.dev.end(), [](const TxidSlice& a, const TxidSlice& b) { return a.len > b.len; });
-}
-// rows[32 k ..]: the hash of hs[k], by the kernel's routine on up to 16 threads (each slice copied under the
-// arena rule of zg_blocks.h: the caller's buffer is neither aligned nor padded)
-static void txid_host_rows(const uint8_t* arena, const std::vector<TxidSlice>& hs, std::vector<uint8_t>& rows) {
-  rows.assign(32 * hs.size() + 1, 0);
-  const size_t nt = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), hs.size()});
-  auto work = [&](size_t t) {
-    TxidArena tmp;
-    for (size_t k = t; k < hs.size(); k += nt) txid_hash_bytes(arena + hs[k].off, hs[k].len, tmp, &rows[32 * k]);
-  };
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < nt; t++) th.emplace_back(work, t);
-  if (nt) work(0);
-  for (auto& t : th) t.join();
-}
-
-extern "C" int zg_txids(zg_ctx* ctx, size_t n, const uint8_t* arena, const uint64_t* off, uint8_t* hashes) {
-  if (!ctx || (n && (!arena || !off || !hashes)) || n > (1u << 30)) return ZG_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return ZG_E_INVAL;
-  if (n && off[n] - off[0] > (1ull << 31)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint64_t base0 = off[0];
-  const size_t bytes = (size_t)(off[n] - base0);
-  std::vector<TxidSlice> all(n);
-  for (size_t i = 0; i < n; i++) all[i] = TxidSlice{(uint32_t)(off[i] - base0), (uint32_t)(off[i + 1] - off[i]), (uint32_t)i, 0};
-  TxidPlan P;
-  txid_plan(ctx, all, P);
-  DevScratch s;
-  uint8_t *darena, *dids;
-  TxidSlice* dsl;
-  HIPCHK(s.alloc(&darena, txid_arena_bytes(bytes)));
-  HIPCHK(s.alloc(&dids, 32 * n));
-  HIPCHK(s.alloc(&dsl, sizeof(TxidSlice) * (P.dev.size() + 1)));
-  if (bytes) HIPCHK(hipMemcpyAsync(darena, arena + base0, bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (!P.dev.empty())
-    HIPCHK(hipMemcpyAsync(dsl, P.dev.data(), sizeof(TxidSlice) * P.dev.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] { return launch_txid(ctx->stream, darena, dsl, (int)P.dev.size(), dids); }));
-  std::vector<uint8_t> hrows;
-  txid_host_rows(arena + base0, P.host, hrows);  // while the kernel runs
-  HIPCHK(hipMemcpyAsync(hashes, dids, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  for (size_t k = 0; k < P.host.size(); k++) memcpy(hashes + (size_t)32 * P.host[k].slot, &hrows[32 * k], 32);
-  return ZG_OK;
-}
-
-extern "C" int zg_blocks_verify(zg_ctx* ctx, size_t nblk, const uint8_t* blocks, const uint64_t* blk_off,
-                                uint64_t max_block_size, uint64_t max_block_sigops, size_t txid_cap, uint8_t* status,
-                                uint8_t* flags, uint64_t* detail, uint8_t* roots, uint64_t* tx_count, uint8_t* txids) {
-  if (!ctx || (nblk && (!blocks || !blk_off || !status || !tx_count)) || nblk > (1u << 20)) return ZG_E_INVAL;
-  for (size_t b = 0; b < nblk; b++)
-    if (blk_off[b + 1] < blk_off[b]) return ZG_E_INVAL;
-  if (nblk && blk_off[nblk] - blk_off[0] > (1ull << 31)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (tx_count) tx_count[0] = 0;
-  if (!nblk) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint64_t base0 = blk_off[0];
-  const size_t bytes = (size_t)(blk_off[nblk] - base0);
-  DevScratch s;
-  uint8_t* darena;
-  HIPCHK(s.alloc(&darena, txid_arena_bytes(bytes)));
-  if (bytes) HIPCHK(hipMemcpyAsync(darena, blocks + base0, bytes, hipMemcpyHostToDevice, ctx->stream));
-
-  // the layouts, on host threads while the arena travels: every offset a lane follows is checked here
-  std::vector<BlockLayout> B(nblk);
-  std::vector<uint32_t> pst(nblk);
-  {
-    const size_t nt = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), nblk});
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-      for (size_t b; (b = next.fetch_add(1)) < nblk;)
-        pst[b] = block_layout(blocks + blk_off[b], (size_t)(blk_off[b + 1] - blk_off[b]), B[b]);
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-  }
-  std::vector<uint32_t> hb;  // the blocks that are hashed: parsed, canonical, not empty
-  for (size_t b = 0; b < nblk; b++) {
-    const bool hashed = pst[b] == ZG_TXP_OK && B[b].n_tx > 0;
-    if (hashed) hb.push_back((uint32_t)b);
-    tx_count[b + 1] = tx_count[b] + (hashed ? B[b].n_tx : 0);
-  }
-  const size_t total = (size_t)tx_count[nblk];
-  if (txids && total > txid_cap) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return fail(ctx, ZG_E_NOMEM, "zg_blocks_verify: the window holds more transactions than txid_cap");
-  }
-
-  std::vector<uint8_t> ids(32 * total + 1), hroots(32 * hb.size() + 1), hmatch(hb.size() + 1), hrows;
-  if (total) {
-    std::vector<TxidSlice> all;
-    std::vector<MerkleBlk> mb;
-    all.reserve(total);
-    for (uint32_t b : hb) {
-      const uint32_t o = (uint32_t)(blk_off[b] - base0);
-      mb.push_back(MerkleBlk{o, (uint32_t)tx_count[b], (uint32_t)B[b].n_tx, 0});
-      for (size_t t = 0; t < B[b].n_tx; t++)
-        all.push_back(TxidSlice{o + (uint32_t)B[b].tx_off[t], (uint32_t)(B[b].tx_off[t + 1] - B[b].tx_off[t]),
-                                (uint32_t)(tx_count[b] + t), 0});
-    }
-    TxidPlan P;
-    txid_plan(ctx, all, P);
-    uint8_t *dids, *dping, *dpong, *droots, *dmatch;
-    TxidSlice* dsl;
-    MerkleBlk* dmb;
-    HIPCHK(s.alloc(&dids, 32 * total));
-    HIPCHK(s.alloc(&dping, 32 * total));
-    HIPCHK(s.alloc(&dpong, 32 * total));
-    HIPCHK(s.alloc(&droots, 32 * mb.size()));
-    HIPCHK(s.alloc(&dmatch, mb.size()));
-    HIPCHK(s.alloc(&dsl, sizeof(TxidSlice) * (P.dev.size() + 1)));
-    HIPCHK(s.alloc(&dmb, sizeof(MerkleBlk) * mb.size()));
-    if (!P.dev.empty())
-      HIPCHK(hipMemcpyAsync(dsl, P.dev.data(), sizeof(TxidSlice) * P.dev.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dmb, mb.data(), sizeof(MerkleBlk) * mb.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(sig_timed(ctx, [&] {
-      hipError_t e = launch_txid(ctx->stream, darena, dsl, (int)P.dev.size(), dids);
-      if (e != hipSuccess) return e;
-      if (!P.host.empty()) {  // the host's share while k_txid runs; its rows join the kernel's before the trees
-        txid_host_rows(blocks + base0, P.host, hrows);
-        for (size_t k = 0; k < P.host.size() && e == hipSuccess; k++)
-          e = hipMemcpyAsync(dids + (size_t)32 * P.host[k].slot, &hrows[32 * k], 32, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return e;
-      }
-      return launch_block_merkle(ctx->stream, darena, dmb, (int)mb.size(), dids, dping, dpong, droots, dmatch);
-    }));
-    HIPCHK(hipMemcpyAsync(ids.data(), dids, 32 * total, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hroots.data(), droots, 32 * mb.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hmatch.data(), dmatch, mb.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(sig_sync(ctx));
-  } else {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  if (txids && total) memcpy(txids, ids.data(), 32 * total);
-
-  // BlockVerifier::check's order (verify_block.rs:31-40); uniqueness from the ids, on the host
-  size_t h = 0;
-  std::vector<std::array<uint8_t, 32>> set;
-  for (size_t b = 0; b < nblk; b++) {
-    if (roots) memset(roots + 32 * b, 0, 32);
-    if (flags) flags[b] = 0;
-    if (detail) detail[b] = 0;
-    if (pst[b] != ZG_TXP_OK) {
-      status[b] = pst[b] == ZG_TXP_MALFORMED ? ZG_BLK_MALFORMED : ZG_BLK_NONCANONICAL;
-      continue;
-    }
-    const BlockLayout& L = B[b];
-    uint32_t f = 0;
-    if (L.n_tx == 0) f |= ZG_BLK_F_EMPTY;
-    if (!L.coinbase0) f |= ZG_BLK_F_COINBASE;
-    if (L.size > max_block_size) f |= ZG_BLK_F_SIZE;
-    if (L.extra_coinbase != BLOCK_NO_INDEX) f |= ZG_BLK_F_EXTRA_COINBASE;
-    if (L.sigops > max_block_sigops) f |= ZG_BLK_F_SIGOPS;
-    if (L.n_tx) {
-      set.resize((size_t)L.n_tx);
-      memcpy(set.data(), &ids[32 * (size_t)tx_count[b]], 32 * (size_t)L.n_tx);
-      std::sort(set.begin(), set.end());
-      if (std::adjacent_find(set.begin(), set.end()) != set.end()) f |= ZG_BLK_F_DUPLICATED;
-      if (!hmatch[h]) f |= ZG_BLK_F_MERKLE_ROOT;
-      if (roots) memcpy(roots + 32 * b, &hroots[32 * h], 32);
-      h++;
-    }
-    status[b] = f & ZG_BLK_F_EMPTY ? ZG_BLK_EMPTY : f & ZG_BLK_F_COINBASE ? ZG_BLK_COINBASE : f & ZG_BLK_F_SIZE ? ZG_BLK_SIZE
-              : f & ZG_BLK_F_EXTRA_COINBASE ? ZG_BLK_EXTRA_COINBASE : f & ZG_BLK_F_DUPLICATED ? ZG_BLK_DUPLICATED
-              : f & ZG_BLK_F_SIGOPS ? ZG_BLK_SIGOPS : f & ZG_BLK_F_MERKLE_ROOT ? ZG_BLK_MERKLE_ROOT : ZG_BLK_OK;
-    if (flags) flags[b] = (uint8_t)f;
-    if (detail) detail[b] = status[b] == ZG_BLK_SIZE ? L.size : status[b] == ZG_BLK_EXTRA_COINBASE ? L.extra_coinbase : 0;
-  }
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ block headers (zg_equihash.h)
-extern "C" int zg_equihash_verify(zg_ctx* ctx, int params, size_t n, const uint8_t* inputs, size_t input_len,
-                                  const uint8_t* solutions, uint8_t* ok, uint8_t* repeated) {
-  const size_t sb = (size_t)equihash_solution_bytes(params);
-  if (!ctx || !sb || input_len < 1 || input_len > 252 || (n && (!inputs || !solutions || !ok)) || n > (1u << 30))
-    return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  DevScratch s;
-  uint8_t *din, *dsol, *dok, *drep;
-  HIPCHK(s.alloc(&din, input_len * n));
-  HIPCHK(s.alloc(&dsol, sb * n));
-  HIPCHK(s.alloc(&dok, n));
-  HIPCHK(s.alloc(&drep, n));
-  HIPCHK(hipMemcpyAsync(din, inputs, input_len * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dsol, solutions, sb * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] {
-    return launch_equihash(ctx->stream, params, din, input_len, (int)input_len, dsol, sb, (int)n, dok, drep);
-  }));
-  HIPCHK(hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (repeated) HIPCHK(hipMemcpyAsync(repeated, drep, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  return ZG_OK;
-}
-
-extern "C" int zg_headers_verify(zg_ctx* ctx, size_t n, const uint8_t* headers, uint32_t max_bits, uint8_t* status,
-                                 uint8_t* hashes, uint8_t* flags) {
-  if (!ctx || (n && (!headers || !status)) || n > (1u << 20)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  DevScratch s;
-  uint8_t *dh, *dok, *drep, *dst, *dhash, *dfl;
-  HIPCHK(s.alloc(&dh, (size_t)ZG_HEADER_BYTES * n));
-  HIPCHK(s.alloc(&dok, n));
-  HIPCHK(s.alloc(&drep, n));
-  HIPCHK(s.alloc(&dst, n));
-  HIPCHK(s.alloc(&dhash, 32 * n));
-  HIPCHK(s.alloc(&dfl, n));
-  HIPCHK(hipMemcpyAsync(dh, headers, (size_t)ZG_HEADER_BYTES * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] { return launch_headers(ctx->stream, dh, (int)n, max_bits, dok, drep, dst, dhash, dfl); }));
-  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (hashes) HIPCHK(hipMemcpyAsync(hashes, dhash, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (flags) HIPCHK(hipMemcpyAsync(flags, dfl, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(sig_sync(ctx));
-  return ZG_OK;
-}
-
-extern "C" int zg_sapling_bvk(zg_ctx* ctx, size_t ntx, const uint32_t* n_spends, const uint32_t* n_outputs,
-                              const uint8_t* cvs, const int64_t* value_balance, uint8_t* bvk, uint8_t* status) {
-  if (!ctx || (ntx && (!n_spends || !n_outputs || !value_balance || !bvk || !status)) || ntx > (1u << 30))
-    return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!ntx) return ZG_OK;
-  std::vector<uint32_t> off(ntx + 1, 0);
-  for (size_t t = 0; t < ntx; t++) {
-    const uint64_t next = (uint64_t)off[t] + n_spends[t] + n_outputs[t];
-    if (next > (1u << 30)) return fail(ctx, ZG_E_INVAL, "too many value commitments");
-    off[t + 1] = (uint32_t)next;
-  }
-  if (off[ntx] && !cvs) return ZG_E_INVAL;
-  HIPCHK(hipSetDevice(ctx->device));
-  const uint32_t* comb = nullptr;
-  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
-                      "Jubjub comb tables", &comb);
-  if (rc) return rc;
-  DevScratch s;
-  uint32_t *doff, *dns;
-  uint8_t *dcv, *dbvk, *dst;
-  int64_t* dvb;
-  HIPCHK(s.alloc(&doff, sizeof(uint32_t) * (ntx + 1)));
-  HIPCHK(s.alloc(&dns, sizeof(uint32_t) * ntx));
-  HIPCHK(s.alloc(&dcv, (size_t)32 * off[ntx]));
-  HIPCHK(s.alloc(&dvb, sizeof(int64_t) * ntx));
-  HIPCHK(s.alloc(&dbvk, 32 * ntx));
-  HIPCHK(s.alloc(&dst, ntx));
-  HIPCHK(hipMemcpyAsync(doff, off.data(), sizeof(uint32_t) * (ntx + 1), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dns, n_spends, sizeof(uint32_t) * ntx, hipMemcpyHostToDevice, ctx->stream));
-  if (off[ntx]) HIPCHK(hipMemcpyAsync(dcv, cvs, (size_t)32 * off[ntx], hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dvb, value_balance, sizeof(int64_t) * ntx, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(launch_sapling_bvk(ctx->stream, (int)ntx, doff, dns, dcv, dvb, comb, dbvk, dst));
-  HIPCHK(hipMemcpyAsync(bvk, dbvk, 32 * ntx, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(status, dst, ntx, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return ZG_OK;
-}
-
-extern "C" int zg_jubjub_decode(zg_ctx* ctx, size_t n, const uint8_t* points, uint8_t* status, uint8_t* xy) {
-  if (!ctx || (n && (!points || !status)) || n > (1u << 30)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  DevScratch s;
-  uint8_t *dp, *dst, *dxy = nullptr;
-  HIPCHK(s.alloc(&dp, 32 * n));
-  HIPCHK(s.alloc(&dst, n));
-  if (xy) HIPCHK(s.alloc(&dxy, 64 * n));
-  HIPCHK(hipMemcpyAsync(dp, points, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(launch_jj_decode(ctx->stream, dp, (int)n, dst, dxy));
-  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (xy) HIPCHK(hipMemcpyAsync(xy, dxy, 64 * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return ZG_OK;
-}
-
-// ------------------------------------------------------------------ host input preparation
-// (zg_prep.h). CPU only: no context, no GPU.
-extern "C" int zg_prep_spend(const uint8_t cv[32], const uint8_t anchor[32], const uint8_t nullifier[32],
-                             const uint8_t rk[32], uint8_t inputs[7 * 32]) {
-  if (!cv || !anchor || !nullifier || !rk || !inputs) return ZG_E_INVAL;
-  return prep_spend(cv, anchor, nullifier, rk, inputs);
-}
-
-extern "C" int zg_prep_output(const uint8_t cv[32], const uint8_t cmu[32], const uint8_t epk[32],
-                              uint8_t inputs[5 * 32]) {
-  if (!cv || !cmu || !epk || !inputs) return ZG_E_INVAL;
-  return prep_output(cv, cmu, epk, inputs);
-}
-
-// A window's preparation in one call: the Sapling descriptions on the GPU (k_prep_sapling, zg_jubjub.hip),
-// the JoinSplits on host threads while it runs (BLAKE2b is host code; ~17 us each), then their rows
-// over the kernel's. Per description the same results as the single functions above (tests/
-// test_gpu_prep_batch.py): a window of 9,609 descriptions took ~380 ms through per-description host
-// calls from a Python thread pool (its per-task overhead under the GIL, not the C, was the bound).
-extern "C" int zg_prep_batch(zg_ctx* ctx, size_t n, const uint8_t* kinds, const uint8_t* fields, uint8_t* inputs,
-                             uint8_t* codes) {
-  if (!ctx || (n && (!kinds || !fields || !inputs || !codes)) || n > (1u << 26)) return ZG_E_INVAL;
-  std::vector<size_t> js;
-  size_t nsap = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (kinds[i] > ZG_PREP_KIND_JOINSPLIT_BN) return ZG_E_INVAL;
-    if (kinds[i] <= ZG_PREP_KIND_OUTPUT)
-      nsap++;
-    else
-      js.push_back(i);
-  }
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!n) return ZG_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (nsap) {  // one grow-only device buffer: kinds | fields | rows | codes
-    const size_t need = n * (2 + ZG_PREP_FIELD_BYTES + 288) + 64;
-    if (ctx->prep_arena_cap < need) {
-      if (ctx->prep_arena) HIPCHK(hipFree(ctx->prep_arena));
-      ctx->prep_arena = nullptr;
-      ctx->prep_arena_cap = 0;
-      HIPCHK(hipMalloc((void**)&ctx->prep_arena, need));
-      ctx->prep_arena_cap = need;
-    }
-    uint8_t* const dk = ctx->prep_arena;
-    uint8_t* const df = dk + n;
-    uint8_t* const din = df + (size_t)ZG_PREP_FIELD_BYTES * n;
-    uint8_t* const dc = din + (size_t)288 * n;
-    HIPCHK(hipMemcpyAsync(dk, kinds, n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(df, fields, (size_t)ZG_PREP_FIELD_BYTES * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_prep_sapling(ctx->stream, dk, df, (int)n, din, dc));
-    HIPCHK(hipMemcpyAsync(inputs, din, (size_t)288 * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(codes, dc, n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  // the JoinSplits meanwhile, into their own rows (written over the copied-back buffer after the sync)
-  std::vector<uint8_t> jrows(js.size() * 288, 0);
-  auto work = [&](size_t lo, size_t hi) {
-    for (size_t k = lo; k < hi; k++) {
-      const uint8_t* f = fields + (size_t)ZG_PREP_FIELD_BYTES * js[k];
-      uint64_t vo = 0, vn = 0;
-      for (int b = 7; b >= 0; b--) {
-        vo = (vo << 8) | f[288 + b];
-        vn = (vn << 8) | f[296 + b];
-      }
-      prep_joinsplit_bits(f, f + 32, f + 64, f + 96, f + 128, f + 160, f + 192, f + 224, vo, vn, f + 256,
-                          kinds[js[k]] == ZG_PREP_KIND_JOINSPLIT ? 254 : 253, &jrows[288 * k]);
-    }
-  };
-  const size_t nt = std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()), js.size() / 64 + 1});
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < nt; t++) th.emplace_back(work, js.size() * t / nt, js.size() * (t + 1) / nt);
-  work(0, js.size() / nt);
-  for (auto& t : th) t.join();
-  if (nsap) {
-    HIPCHK(hipEventRecord(ctx->ev[13], ctx->stream));
-    HIPCHK(wait_event(ctx->ev[13]));
-  }
-  for (size_t k = 0; k < js.size(); k++) {
-    memcpy(inputs + (size_t)288 * js[k], &jrows[288 * k], 288);
-    codes[js[k]] = ZG_PREP_OK;
-  }
-  return ZG_OK;
-}
-
-extern "C" int zg_hsig(const uint8_t random_seed[32], const uint8_t nf0[32], const uint8_t nf1[32],
-                       const uint8_t pubkey[32], uint8_t out[32]) {
-  if (!random_seed || !nf0 || !nf1 || !pubkey || !out) return ZG_E_INVAL;
-  prep_hsig(random_seed, nf0, nf1, pubkey, out);
-  return ZG_OK;
-}
-
-extern "C" int zg_prep_joinsplit(const uint8_t anchor[32], const uint8_t random_seed[32],
-                                 const uint8_t nullifiers[64], const uint8_t macs[64],
-                                 const uint8_t commitments[64], uint64_t vpub_old, uint64_t vpub_new,
-                                 const uint8_t pubkey[32], uint8_t inputs[9 * 32]) {
-  if (!anchor || !random_seed || !nullifiers || !macs || !commitments || !pubkey || !inputs) return ZG_E_INVAL;
-  prep_joinsplit(anchor, random_seed, nullifiers, nullifiers + 32, macs, macs + 32, commitments, commitments + 32,
-                 vpub_old, vpub_new, pubkey, inputs);
-  return ZG_OK;
-}
-
-extern "C" int zg_prep_joinsplit_bn(const uint8_t anchor[32], const uint8_t random_seed[32],
-                                    const uint8_t nullifiers[64], const uint8_t macs[64],
-                                    const uint8_t commitments[64], uint64_t vpub_old, uint64_t vpub_new,
-                                    const uint8_t pubkey[32], uint8_t inputs[9 * 32]) {
-  if (!anchor || !random_seed || !nullifiers || !macs || !commitments || !pubkey || !inputs) return ZG_E_INVAL;
-  prep_joinsplit_bits(anchor, random_seed, nullifiers, nullifiers + 32, macs, macs + 32, commitments,
-                      commitments + 32, vpub_old, vpub_new, pubkey, 253, inputs);
-  return ZG_OK;
-}
-
 // ------------------------------------------------------------------ synthetic workload
 static void reduce_mod_r(uint8_t* le32) {
   // value < 2^256 < 3r: subtract r while >= r
@@ -2244,15 +1290,8 @@ extern "C" int zg_synth_rerandomize(zg_ctx* ctx, size_t n_src, const uint8_t* sr
     if (src_index[i] >= n_src) return fail(ctx, ZG_E_INVAL, "src_index out of range");
   std::vector<uint32_t> ts(16 * n);
   for (size_t i = 0; i < n; i++) {
-    Blake2b h(64);
-    h.update("zg-rerand", 9);
-    uint8_t le[8];
-    for (int b = 0; b < 8; b++) le[b] = (uint8_t)(seed >> (8 * b));
-    h.update(le, 8);
-    for (int b = 0; b < 8; b++) le[b] = (uint8_t)((uint64_t)i >> (8 * b));
-    h.update(le, 8);
     uint8_t dg[64];
-    h.final(dg);
+    seeded_bytes("zg-rerand", seed, i, dg, 64);
     for (int half = 0; half < 2; half++) {
       uint8_t* x = dg + 32 * half;
       reduce_mod_r(x);
@@ -2264,32 +1303,27 @@ extern "C" int zg_synth_rerandomize(zg_ctx* ctx, size_t n_src, const uint8_t* sr
                                     ((uint32_t)x[4 * w + 2] << 16) | ((uint32_t)x[4 * w + 3] << 24);
     }
   }
+  DevScratch s;
   uint8_t *d_src, *d_sk, *d_out;
   uint32_t *d_idx, *d_ts;
-  HIPCHK(hipMalloc(&d_src, 192 * n_src));
-  HIPCHK(hipMalloc(&d_sk, n_src));
-  HIPCHK(hipMalloc(&d_out, 192 * (n ? n : 1)));
-  HIPCHK(hipMalloc(&d_idx, 4 * (n ? n : 1)));
-  HIPCHK(hipMalloc(&d_ts, 64 * (n ? n : 1)));
-  int rc = ZG_OK;
+  HIPCHK(s.alloc(&d_src, 192 * n_src));
+  HIPCHK(s.alloc(&d_sk, n_src));
+  HIPCHK(s.alloc(&d_out, 192 * n));
+  HIPCHK(s.alloc(&d_idx, 4 * n));
+  HIPCHK(s.alloc(&d_ts, 64 * n));
   if (hipMemcpy(d_src, src_proofs, 192 * n_src, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d_sk, src_kinds, n_src, hipMemcpyHostToDevice) != hipSuccess ||
       (n && hipMemcpy(d_idx, src_index, 4 * n, hipMemcpyHostToDevice) != hipSuccess) ||
-      (n && hipMemcpy(d_ts, ts.data(), 64 * n, hipMemcpyHostToDevice) != hipSuccess)) {
-    rc = fail(ctx, ZG_E_HIP, "copy");
-  } else if (n) {
+      (n && hipMemcpy(d_ts, ts.data(), 64 * n, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(ctx, ZG_E_HIP, "copy");
+  if (n) {
     hipLaunchKernelGGL(k_rerandomize, dim3(nblocks(n)), dim3(ZG_BLOCK), 0, ctx->stream, ctx->d_vk, d_src, d_sk, d_idx,
                        d_ts, (int)n, d_out);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(out_proofs, d_out, 192 * n, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(ctx, ZG_E_HIP, "rerandomize kernel");
+      return fail(ctx, ZG_E_HIP, "rerandomize kernel");
   }
-  hipFree(d_src);
-  hipFree(d_sk);
-  hipFree(d_out);
-  hipFree(d_idx);
-  hipFree(d_ts);
-  return rc;
+  return ZG_OK;
 }
 
 extern "C" int zg_bench_mad_rate(zg_ctx* ctx, double* macs_per_s) { return zg_bench_mad_rate_clock(ctx, macs_per_s, nullptr); }
@@ -2299,8 +1333,9 @@ extern "C" int zg_bench_mad_rate_clock(zg_ctx* ctx, double* macs_per_s, double* 
   std::lock_guard<std::mutex> g(ctx->mu);
   HIPCHK(hipSetDevice(ctx->device));
   const int blocks = 256 * 16, threads = 256, iters = 2048;
+  DevScratch s;
   uint64_t* d_st = nullptr;
-  HIPCHK(hipMalloc(&d_st, sizeof(uint64_t) * 2 * blocks));
+  HIPCHK(s.alloc(&d_st, sizeof(uint64_t) * 2 * blocks));
   hipLaunchKernelGGL(k_mad_rate, dim3(blocks), dim3(threads), 0, ctx->stream, (uint64_t*)ctx->d_int, 16, 1u,
                      (uint64_t*)nullptr);
   hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -2315,7 +1350,6 @@ extern "C" int zg_bench_mad_rate_clock(zg_ctx* ctx, double* macs_per_s, double* 
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
   std::vector<uint64_t> st(2 * blocks);
   if (e == hipSuccess) e = hipMemcpy(st.data(), d_st, sizeof(uint64_t) * 2 * blocks, hipMemcpyDeviceToHost);
-  hipFree(d_st);
   if (e != hipSuccess) return fail(ctx, ZG_E_HIP, std::string("mad rate probe: ") + hipGetErrorString(e));
   *macs_per_s = (double)blocks * threads * iters * 64.0 / (ms * 1e-3);
   if (clock_hz) {  // median over blocks of shader ticks / (constant ticks / 100 MHz)
@@ -2338,188 +1372,14 @@ extern "C" int zg_chacha20_blocks(zg_ctx* ctx, const uint8_t key[32], const uint
   ChachaKey k;
   memcpy(k.key, key, 32);
   memcpy(k.nonce, nonce, 12);
+  DevScratch s;
   uint4* d = nullptr;
-  HIPCHK(hipMalloc(&d, 64 * nblocks));
+  HIPCHK(s.alloc(&d, 64 * nblocks));
   hipLaunchKernelGGL(k_chacha20, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, ctx->stream, k, counter,
                      nblocks, d);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(out, d, 64 * nblocks, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
   if (e != hipSuccess) return fail(ctx, ZG_E_HIP, std::string("zg_chacha20_blocks: ") + hipGetErrorString(e));
   return ZG_OK;
-}
-
-// ------------------------------------------------------------------ note-commitment trees (zg_merkle.hip)
-static zg::MerkleDev* merkle_dev(zg_ctx* ctx) {
-  zg_dev* d = ctx->dev;
-  std::lock_guard<std::mutex> g(d->mu);
-  if (!d->merkle) d->merkle = merkle_dev_new();
-  return d->merkle;
-}
-
-extern "C" int zg_merkle_combine(zg_ctx* ctx, int kind, size_t n, const uint8_t* left, const uint8_t* right,
-                                 const uint8_t* depth, uint8_t* out) {
-  if (!ctx || (kind != ZG_TREE_SPROUT && kind != ZG_TREE_SAPLING) || (n && (!left || !right || !out)) ||
-      n > (1u << 30))
-    return ZG_E_INVAL;
-  if (kind == ZG_TREE_SAPLING && depth)
-    for (size_t i = 0; i < n; i++)
-      if (depth[i] >= 63) return fail(ctx, ZG_E_INVAL, "MerkleTree depth must be < 63");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  return merkle_combine(merkle_dev(ctx), ctx->stream, kind, n, left, right, depth, out, &ctx->err);
-}
-
-extern "C" int zg_tree_empty_roots(zg_ctx* ctx, int kind, size_t levels, uint8_t* out) {
-  if (!ctx || (kind != ZG_TREE_SPROUT && kind != ZG_TREE_SAPLING) || levels > 64 || (levels && !out))
-    return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  return merkle_empty_roots(merkle_dev(ctx), ctx->stream, kind, levels, out, &ctx->err);
-}
-
-extern "C" size_t zg_tree_state_max_bytes(int height) { return merkle_state_max_bytes(height); }
-
-static int tree_roots(zg_ctx* ctx, int kind, int height, const uint8_t* state, size_t state_len, size_t n,
-                      const void* leaves, int on_device, size_t n_marks, const uint64_t* marks, uint8_t* roots,
-                      uint8_t* state_out, size_t* state_out_len, float* kernel_ms) {
-  if (!ctx || (kind != ZG_TREE_SPROUT && kind != ZG_TREE_SAPLING) || height < 1 || height > 62 ||
-      (n && !leaves) || (n_marks && (!marks || !roots)) || (state_len && !state) || n > (1ull << 40) ||
-      n_marks > (1u << 30))
-    return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  return merkle_tree_roots(merkle_dev(ctx), ctx->stream, kind, height, state, state_len, n, leaves, on_device,
-                           n_marks, marks, roots, state_out, state_out_len, kernel_ms, &ctx->tree_arena,
-                           &ctx->tree_arena_cap, &ctx->err);
-}
-
-extern "C" int zg_tree_roots(zg_ctx* ctx, int kind, int height, const uint8_t* state, size_t state_len,
-                             size_t n_leaves, const uint8_t* leaves, size_t n_marks, const uint64_t* marks,
-                             uint8_t* roots, uint8_t* state_out, size_t* state_out_len) {
-  return tree_roots(ctx, kind, height, state, state_len, n_leaves, leaves, 0, n_marks, marks, roots, state_out,
-                    state_out_len, nullptr);
-}
-
-extern "C" int zg_tree_roots_device(zg_ctx* ctx, int kind, int height, const uint8_t* state, size_t state_len,
-                                    size_t n_leaves, const void* d_leaves, size_t n_marks, const uint64_t* marks,
-                                    uint8_t* roots, uint8_t* state_out, size_t* state_out_len, float* kernel_ms) {
-  return tree_roots(ctx, kind, height, state, state_len, n_leaves, d_leaves, 1, n_marks, marks, roots, state_out,
-                    state_out_len, kernel_ms);
-}
-
-// ------------------------------------------------------------------ PGHR13 Sprout proofs (zg_pghr13.hip)
-static zg::BnDev* bn_dev(zg_ctx* ctx) {
-  zg_dev* d = ctx->dev;
-  std::lock_guard<std::mutex> g(d->mu);
-  if (!d->bn) d->bn = bn_dev_new();
-  return d->bn;
-}
-
-// a key is parsed, prepared into fresh buffers and published in the device cache, then this
-// context points at it (other contexts keep theirs); a failed load leaves the context's key as it was
-static int pghr13_load_locked(zg_ctx* ctx, const char* json, size_t len) {
-  HIPCHK(hipSetDevice(ctx->device));
-  const zg::BnKey* k = nullptr;
-  zg::BnDev* d = bn_dev(ctx);
-  const int rc = bn_load_vk_json(d, ctx->stream, json, len, &k, &ctx->err);
-  if (rc == ZG_OK) {
-    if (ctx->bn_key) bn_key_release(d, ctx->bn_key);  // the old key goes once no context uses it
-    ctx->bn_key = k;
-  }
-  return rc;
-}
-
-extern "C" int zg_pghr13_vk_load_json(zg_ctx* ctx, const char* json, size_t len) {
-  if (!ctx || !json) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return pghr13_load_locked(ctx, json, len);
-}
-
-extern "C" int zg_pghr13_vk_load_builtin(zg_ctx* ctx) {
-  return zg_pghr13_vk_load_json(ctx, ZG_PGHR13_VK_JSON, strlen(ZG_PGHR13_VK_JSON));
-}
-
-extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* inputs,
-                                const uint8_t* n_inputs, uint8_t* status, float* kernel_ms) {
-  if (!ctx || (n && (!proofs || !inputs || !status)) || n > (1u << 24)) return ZG_E_INVAL;
-  if (n_inputs)
-    for (size_t i = 0; i < n; i++)
-      if (n_inputs[i] > 9) return fail(ctx, ZG_E_INVAL, "at most 9 PGHR13 inputs per proof");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!ctx->bn_key) {  // first use: the builtin key (res/sprout-verifying-key.json)
-    int rc = pghr13_load_locked(ctx, ZG_PGHR13_VK_JSON, strlen(ZG_PGHR13_VK_JSON));
-    if (rc) return rc;
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!n) return ZG_OK;
-  // the equality weights rho_2..rho_5 and rho_1 (16 bytes each, zg_pghr13.hip ZG_PGHR_RHO_BYTES):
-  // seeded contexts (tests) derive them, others take them from the OS
-  std::vector<uint8_t> rho(80 * n);
-  if (ctx->seeded) {
-    for (size_t i = 0; i < n; i++) {
-      uint8_t le[8], h1[64];
-      Blake2b h(64);
-      h.update("zg-pghr13-rho", 13);
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)(ctx->seed >> (8 * b));
-      h.update(le, 8);
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)((uint64_t)i >> (8 * b));
-      h.update(le, 8);
-      h.final(&rho[80 * i]);
-      Blake2b g(64);
-      g.update("zg-pghr13-rho1", 14);
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)(ctx->seed >> (8 * b));
-      g.update(le, 8);
-      for (int b = 0; b < 8; b++) le[b] = (uint8_t)((uint64_t)i >> (8 * b));
-      g.update(le, 8);
-      g.final(h1);
-      memcpy(&rho[80 * i + 64], h1, 16);
-    }
-  } else if (!os_random(rho.data(), rho.size())) {
-    return fail(ctx, ZG_E_INVAL, "getrandom failed");
-  }
-  // one batch check per chunk of at most ctx->pghr_chunk proofs: the call's arena (~27 KB per proof,
-  // mostly the b lines) stays bounded at the chunk size however large the caller's window is
-  if (kernel_ms) *kernel_ms = 0;
-  bool any_failed = false;
-  const size_t chunk = ctx->pghr_chunk;
-  for (size_t o = 0; o < n; o += chunk) {
-    const size_t m = n - o < chunk ? n - o : chunk;
-    bool batch_failed = false;
-    float ms = 0;
-    const int rc = bn_pghr13_verify(ctx->bn_key, ctx->stream, ctx->side, m, ctx->pghr_straus_b, ctx->pghr_bseg_k,
-                                    proofs + 296 * o, inputs + 9 * 32 * o, n_inputs ? n_inputs + o : nullptr,
-                                    rho.data() + 80 * o, status + o, kernel_ms ? &ms : nullptr, &batch_failed,
-                                    &ctx->bn_arena, &ctx->bn_arena_cap, &ctx->err);
-    if (rc != ZG_OK) return rc;
-    if (kernel_ms) *kernel_ms += ms;
-    any_failed = any_failed || batch_failed;
-  }
-  if (n) {  // once per call, however many chunks it took (include/zg.h zg_stats [8], [9])
-    ctx->stats[8]++;
-    if (any_failed) ctx->stats[9]++;
-  }
-  return ZG_OK;
-}
-
-extern "C" int zg_pghr13_shape(zg_ctx* ctx, size_t n, int* straus_b, int* bseg_k, size_t* chunk, int* halves,
-                               int* p7_side) {
-  if (!ctx) return ZG_E_INVAL;
-  const size_t first = n < ctx->pghr_chunk ? n : ctx->pghr_chunk;
-  int B, K, hv, p7;
-  bn_pghr13_shape(first, ctx->pghr_straus_b, ctx->pghr_bseg_k, &B, &K, &hv, &p7);
-  if (straus_b) *straus_b = B;
-  if (bseg_k) *bseg_k = K;
-  if (chunk) *chunk = ctx->pghr_chunk;
-  if (halves) *halves = hv;
-  if (p7_side) *p7_side = p7;
-  return ZG_OK;
-}
-
-extern "C" int zg_bn254_pairing(zg_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt) {
-  if (!ctx || (n && (!g1 || !g2 || !gt)) || n > (1u << 20)) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  return bn_pairing(ctx->stream, n, g1, g2, gt, &ctx->err);
 }

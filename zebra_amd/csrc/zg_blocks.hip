@@ -2,7 +2,7 @@
 // slice, dhash256 of a contiguous range of the arena; the host hands the slices over longest first, so a
 // wave's lanes run similar lengths, each hash going to the row its slice names. k_block_merkle: workgroup
 // per block, the Bitcoin merkle tree over that block's rows, the root compared with the header's field.
-// Every offset a lane follows was checked by the host (zg.hip: zg_txids, zg_blocks_verify).
+// Every offset a lane follows was checked by the host (zg_calls.hip: zg_txids, zg_blocks_verify).
 #include <hip/hip_runtime.h>
 
 #include "../../include/zg.h"

@@ -115,6 +115,9 @@ __global__ void k_gather32(int n, const uint32_t* const* src, uint32_t* out) {
 }
 
 // ------------------------------------------------------------------ host side
+}  // namespace zg
+#include "zg_hostkit.h"  // below the kernels: nothing above sees it
+namespace zg {
 struct MerkleDev {
   std::mutex mu;
   uint32_t* ph = nullptr;                                    // Pedersen table (first Sapling use)
@@ -131,28 +134,6 @@ void merkle_dev_free(MerkleDev* m) {
   delete m;
 }
 
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) hipFree(q);
-  }
-  template <class T>
-  hipError_t alloc(T** x, size_t bytes) {
-    hipError_t e = hipMalloc((void**)x, bytes ? bytes : 1);
-    if (e == hipSuccess) p.push_back(*x);
-    return e;
-  }
-};
-
-#define MCHK(expr)                                                         \
-  do {                                                                     \
-    hipError_t e_ = (expr);                                                \
-    if (e_ != hipSuccess) {                                                \
-      *err = std::string(#expr ": ") + hipGetErrorString(e_);              \
-      return ZG_E_HIP;                                                     \
-    }                                                                      \
-  } while (0)
-
 static unsigned blocks64(long long n) { return (unsigned)((n + 63) / 64); }
 
 // the Pedersen table and the kind's empty roots, built once per device
@@ -160,7 +141,7 @@ static int merkle_ready(MerkleDev* m, hipStream_t st, int kind, std::string* err
   std::lock_guard<std::mutex> g(m->mu);
   if (kind == ZG_TREE_SAPLING && !m->ph) {
     uint32_t* t = nullptr;
-    MCHK(hipMalloc(&t, ZG_PH_TABLE_BYTES));
+    HIPCHK_TO(err, hipMalloc(&t, ZG_PH_TABLE_BYTES));
     hipLaunchKernelGGL(k_ph_table, dim3(blocks64(ZG_PH_POINTS)), dim3(64), 0, st, t);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -173,7 +154,7 @@ static int merkle_ready(MerkleDev* m, hipStream_t st, int kind, std::string* err
   }
   if (!m->empty[kind]) {
     uint32_t* e = nullptr;
-    MCHK(hipMalloc(&e, ZG_TREE_EMPTY_LEVELS * 32));
+    HIPCHK_TO(err, hipMalloc(&e, ZG_TREE_EMPTY_LEVELS * 32));
     uint8_t e0[32] = {0};
     e0[0] = kind == ZG_TREE_SAPLING ? 1 : 0;  // pedersen_uncommitted() = Fr one; Sprout: zero
     hipError_t he = hipMemcpyAsync(e, e0, 32, hipMemcpyHostToDevice, st);
@@ -200,27 +181,22 @@ int merkle_combine(MerkleDev* m, hipStream_t st, int kind, size_t n, const uint8
                    const uint8_t* depth, uint8_t* out, std::string* err) {
   int rc = merkle_ready(m, st, kind, err);
   if (rc || !n) return rc;
-  Scratch s;
+  DevScratch s;
   uint32_t *dl, *dr, *dout;
   uint8_t* dd = nullptr;
-  MCHK(s.alloc(&dl, 32 * n));
-  MCHK(s.alloc(&dr, 32 * n));
-  MCHK(s.alloc(&dout, 32 * n));
-  MCHK(hipMemcpyAsync(dl, l, 32 * n, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(dr, r, 32 * n, hipMemcpyHostToDevice, st));
-  if (depth) {
-    MCHK(s.alloc(&dd, n));
-    MCHK(hipMemcpyAsync(dd, depth, n, hipMemcpyHostToDevice, st));
-  }
+  HIPCHK_TO(err, s.up(&dl, l, 32 * n, st));
+  HIPCHK_TO(err, s.up(&dr, r, 32 * n, st));
+  HIPCHK_TO(err, s.alloc(&dout, 32 * n));
+  if (depth) HIPCHK_TO(err, s.up(&dd, depth, n, st));
   if (kind == ZG_TREE_SAPLING)
     hipLaunchKernelGGL((k_merkle_combine<ZG_TREE_SAPLING, ZG_PH_LANES_NARROW>), dim3(blocks64(n * ZG_PH_LANES_NARROW)),
                        dim3(64), 0, st, (int)n, dl, dr, dd, (const uint32_t*)m->ph, dout);
   else
     hipLaunchKernelGGL((k_merkle_combine<ZG_TREE_SPROUT, 1>), dim3(blocks64(n)), dim3(64), 0, st, (int)n, dl, dr, dd,
                        (const uint32_t*)m->ph, dout);
-  MCHK(hipGetLastError());
-  MCHK(hipMemcpyAsync(out, dout, 32 * n, hipMemcpyDeviceToHost, st));
-  MCHK(hipStreamSynchronize(st));
+  HIPCHK_TO(err, hipGetLastError());
+  HIPCHK_TO(err, hipMemcpyAsync(out, dout, 32 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK_TO(err, hipStreamSynchronize(st));
   return ZG_OK;
 }
 
@@ -299,7 +275,7 @@ static void launch_level(hipStream_t st, const TreeLevel& L, int level, int nm, 
 int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const uint8_t* state, size_t state_len,
                       size_t n, const void* leaves, int leaves_on_device, size_t nmarks, const uint64_t* marks,
                       uint8_t* roots, uint8_t* state_out, size_t* state_out_len, float* kernel_ms,
-                      void** arena, size_t* arena_cap, std::string* err) {
+                      DevArena& arena, std::string* err) {
   if (height < 1 || height > 62 || (kind != ZG_TREE_SPROUT && kind != ZG_TREE_SAPLING)) return ZG_E_INVAL;
   HostTree t;
   t.phas.assign(height - 1, 0);
@@ -360,25 +336,16 @@ int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const 
     }
   }
   const int nm = (int)pos.size();
-  // one device allocation per context, reused across calls (grow-only, zg_destroy frees it)
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // the context's arena, every part 256-aligned
+  auto al = [](size_t b) { return Carve::span(b, 256); };
   size_t need = al(32 * (2 + (size_t)height)) + (leaves_on_device ? 0 : al(32 * n_eff)) +
                 al(sizeof(unsigned long long) * (nm + 1)) + al(32 * (size_t)(nm + 1)) +
                 2 * al(32 * (size_t)(height + 1));
   for (int l = 1; l < height; l++) need += al(32 * (size_t)lcnt[l]);
-  if (*arena_cap < need) {
-    if (*arena) hipFree(*arena);
-    *arena = nullptr;
-    *arena_cap = 0;
-    MCHK(hipMalloc(arena, need));
-    *arena_cap = need;
-  }
-  char* bump = (char*)*arena;
-  auto take = [&](size_t b) {
-    char* p = bump;
-    bump += al(b);
-    return (void*)p;
-  };
+  HIPCHK_TO(err, arena.reserve(need, st));
+  // (a part of no bytes is null: the leaves of an empty window, a level with no node. Nothing reads one:
+  // tree_node indexes a level's buffer only inside [base, base + cnt))
+  auto take = [&](size_t b) { return (void*)arena.carve<char>(b, 256); };
   // frontier slots: [0] leaf s0 - 1, [1] leaf s0 - 2, [2 + i] parents[i] (level i + 1)
   std::vector<uint8_t> fh(32 * (2 + height), 0);
   if (s0) {
@@ -389,11 +356,11 @@ int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const 
   for (int i = 0; i < height - 1; i++)
     if (t.phas[i]) memcpy(&fh[32 * (2 + i)], t.par[i].data(), 32);
   uint32_t* dfront = (uint32_t*)take(fh.size());
-  MCHK(hipMemcpyAsync(dfront, fh.data(), fh.size(), hipMemcpyHostToDevice, st));
+  HIPCHK_TO(err, hipMemcpyAsync(dfront, fh.data(), fh.size(), hipMemcpyHostToDevice, st));
   const uint32_t* dleaves = (const uint32_t*)leaves;
   if (!leaves_on_device) {
     uint32_t* dl = (uint32_t*)take(32 * n_eff);
-    if (n_eff) MCHK(hipMemcpyAsync(dl, leaves, 32 * n_eff, hipMemcpyHostToDevice, st));
+    if (n_eff) HIPCHK_TO(err, hipMemcpyAsync(dl, leaves, 32 * n_eff, hipMemcpyHostToDevice, st));
     dleaves = dl;
   }
   const uint32_t* E = m->empty[kind];
@@ -407,12 +374,12 @@ int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const 
   }
   unsigned long long* dpos = (unsigned long long*)take(sizeof(unsigned long long) * (nm + 1));
   uint32_t* dcur = (uint32_t*)take(32 * (size_t)(nm + 1));
-  if (nm) MCHK(hipMemcpyAsync(dpos, pos.data(), sizeof(unsigned long long) * nm, hipMemcpyHostToDevice, st));
+  if (nm) HIPCHK_TO(err, hipMemcpyAsync(dpos, pos.data(), sizeof(unsigned long long) * nm, hipMemcpyHostToDevice, st));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (kernel_ms) {
-    MCHK(hipEventCreate(&e0));
-    MCHK(hipEventCreate(&e1));
-    MCHK(hipEventRecord(e0, st));
+    HIPCHK_TO(err, hipEventCreate(&e0));
+    HIPCHK_TO(err, hipEventCreate(&e1));
+    HIPCHK_TO(err, hipEventRecord(e0, st));
   }
   for (int l = 0; l < height; l++) {
     const bool top = l + 1 == height;
@@ -426,11 +393,11 @@ int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const 
       launch_level<ZG_TREE_SAPLING, ZG_PH_LANES_WIDE>(st, L[l], l, nm, dpos, dcur, wn, bn, cnt_next, m->ph);
     else
       launch_level<ZG_TREE_SAPLING, ZG_PH_LANES_NARROW>(st, L[l], l, nm, dpos, dcur, wn, bn, cnt_next, m->ph);
-    MCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
   }
-  if (kernel_ms) MCHK(hipEventRecord(e1, st));
+  if (kernel_ms) HIPCHK_TO(err, hipEventRecord(e1, st));
   std::vector<uint8_t> cur(32 * (size_t)nm);
-  if (nm) MCHK(hipMemcpyAsync(cur.data(), dcur, cur.size(), hipMemcpyDeviceToHost, st));
+  if (nm) HIPCHK_TO(err, hipMemcpyAsync(cur.data(), dcur, cur.size(), hipMemcpyDeviceToHost, st));
   // the final frontier: left / right = leaves s1 - 1, s1 - 2 by parity; parents[i] = the
   // completed level-(i+1) node left of the last leaf's ancestor when that ancestor is odd
   HostTree fin;
@@ -460,15 +427,15 @@ int merkle_tree_roots(MerkleDev* m, hipStream_t st, int kind, int height, const 
   if (!src.empty() && state_out && !full) {
     const uint32_t** dsrc = (const uint32_t**)take(sizeof(void*) * src.size());
     uint32_t* dout = (uint32_t*)take(fr.size());
-    MCHK(hipMemcpyAsync(dsrc, src.data(), sizeof(void*) * src.size(), hipMemcpyHostToDevice, st));
+    HIPCHK_TO(err, hipMemcpyAsync(dsrc, src.data(), sizeof(void*) * src.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_gather32, dim3(blocks64(8 * (long long)src.size())), dim3(64), 0, st, (int)src.size(),
                        (const uint32_t* const*)dsrc, dout);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(fr.data(), dout, fr.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK_TO(err, hipGetLastError());
+    HIPCHK_TO(err, hipMemcpyAsync(fr.data(), dout, fr.size(), hipMemcpyDeviceToHost, st));
   }
-  MCHK(hipStreamSynchronize(st));
+  HIPCHK_TO(err, hipStreamSynchronize(st));
   if (kernel_ms) {
-    MCHK(hipEventElapsedTime(kernel_ms, e0, e1));
+    HIPCHK_TO(err, hipEventElapsedTime(kernel_ms, e0, e1));
     hipEventDestroy(e0);
     hipEventDestroy(e1);
   }

@@ -868,6 +868,9 @@ __global__ void __launch_bounds__(64) k_bn_gt(int n, Bq12* w, uint32_t* gt) {
 }
 
 // ------------------------------------------------------------------ host side
+}  // namespace zg
+#include "zg_hostkit.h"  // below the kernels: nothing above sees it
+namespace zg {
 // One prepared PGHR13 key: the key, its line table and comb tables. Built into fresh buffers
 // and published in the device's cache only once complete and valid; never modified or freed
 // while the device lives, so a context verifying with it needs no lock (a key loaded on one
@@ -913,15 +916,6 @@ void bn_dev_free(BnDev* d) {
   for (BnKey* k : d->keys) bn_key_free(k);
   delete d;
 }
-
-#define BCHK(expr)                                            \
-  do {                                                        \
-    hipError_t e_ = (expr);                                   \
-    if (e_ != hipSuccess) {                                   \
-      *err = std::string(#expr ": ") + hipGetErrorString(e_); \
-      return ZG_E_HIP;                                        \
-    }                                                         \
-  } while (0)
 
 static unsigned bn_blocks(long long n) { return (unsigned)((n + 63) / 64); }
 // k_pghr_bseg's proofs per lane (forced: the context's ZG_BSEG_K; <= 0: by size): ceil(n / K) >= 8,192
@@ -1076,8 +1070,7 @@ void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* 
 
 int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
                      const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
-                     uint8_t* status, float* kernel_ms, bool* batch_failed, void** arena, size_t* arena_cap,
-                     std::string* err) {
+                     uint8_t* status, float* kernel_ms, bool* batch_failed, DevArena& arena, std::string* err) {
   if (batch_failed) *batch_failed = false;
   if (!n) return ZG_OK;
   int B, K, halves, p7_on_side;
@@ -1088,7 +1081,7 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   struct Part {
     void** p;
     size_t b;
-  };
+  };  // (256-aligned; a part of no bytes, dni without ninputs, is null)
   uint8_t *dp, *din, *dni = nullptr, *drho, *dst, *dokb, *dbst;
   PghrPts *dpts, *dagg;
   PghrDec* ddec;
@@ -1120,20 +1113,9 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
       {(void**)&dbst, ZG_PGHR_FSEG + 1},
   };
   size_t need = 0;
-  for (const Part& q : parts) need += (q.b + 255) & ~(size_t)255;
-  if (*arena_cap < need) {
-    BCHK(hipStreamSynchronize(st));
-    if (*arena) hipFree(*arena);
-    *arena = nullptr;
-    *arena_cap = 0;
-    BCHK(hipMalloc(arena, need));
-    *arena_cap = need;
-  }
-  char* bump = (char*)*arena;
-  for (const Part& q : parts) {
-    *q.p = q.b ? bump : nullptr;
-    bump += (q.b + 255) & ~(size_t)255;
-  }
+  for (const Part& q : parts) need += Carve::span(q.b, 256);
+  HIPCHK_TO(err, arena.reserve(need, st));
+  for (const Part& q : parts) *q.p = arena.carve<char>(q.b, 256);
   struct Events {
     hipEvent_t e[8] = {};
     ~Events() {
@@ -1142,15 +1124,15 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
     }
   } ev;
   hipEvent_t &e0 = ev.e[0], &e1 = ev.e[1], &g2fork = ev.e[4], &g2join = ev.e[5], &g2dec = ev.e[6], &stready = ev.e[7];
-  for (hipEvent_t* x : {&g2fork, &g2join, &g2dec, &stready}) BCHK(hipEventCreateWithFlags(x, hipEventDisableTiming));
-  BCHK(hipMemcpyAsync(dp, proofs, 296 * n, hipMemcpyHostToDevice, st));
-  BCHK(hipMemcpyAsync(din, inputs, 9 * 32 * n, hipMemcpyHostToDevice, st));
-  BCHK(hipMemcpyAsync(drho, rho, ZG_PGHR_RHO_BYTES * n, hipMemcpyHostToDevice, st));
-  if (ninputs) BCHK(hipMemcpyAsync(dni, ninputs, n, hipMemcpyHostToDevice, st));
+  for (hipEvent_t* x : {&g2fork, &g2join, &g2dec, &stready}) HIPCHK_TO(err, hipEventCreateWithFlags(x, hipEventDisableTiming));
+  HIPCHK_TO(err, hipMemcpyAsync(dp, proofs, 296 * n, hipMemcpyHostToDevice, st));
+  HIPCHK_TO(err, hipMemcpyAsync(din, inputs, 9 * 32 * n, hipMemcpyHostToDevice, st));
+  HIPCHK_TO(err, hipMemcpyAsync(drho, rho, ZG_PGHR_RHO_BYTES * n, hipMemcpyHostToDevice, st));
+  if (ninputs) HIPCHK_TO(err, hipMemcpyAsync(dni, ninputs, n, hipMemcpyHostToDevice, st));
   if (kernel_ms) {
-    BCHK(hipEventCreate(&e0));
-    BCHK(hipEventCreate(&e1));
-    BCHK(hipEventRecord(e0, st));
+    HIPCHK_TO(err, hipEventCreate(&e0));
+    HIPCHK_TO(err, hipEventCreate(&e1));
+    HIPCHK_TO(err, hipEventRecord(e0, st));
   }
   // b's decode (Fq2 sqrt + G2 membership) and its lines (lane per proof at ~280 registers: one
   // wave per SIMD) on the side stream, sharing the SIMDs with the G1 decodes, combs, prep and rho
@@ -1160,35 +1142,35 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
     hipStream_t s;
     ~SideJoin() { hipStreamSynchronize(s); }
   } side_join{side};
-  BCHK(hipEventRecord(g2fork, st));
-  BCHK(hipStreamWaitEvent(side, g2fork, 0));
+  HIPCHK_TO(err, hipEventRecord(g2fork, st));
+  HIPCHK_TO(err, hipStreamWaitEvent(side, g2fork, 0));
   hipLaunchKernelGGL(k_pghr_decode_g2, dim3(nb), dim3(64), 0, side, (int)n, dp, ddec, dokb);
-  BCHK(hipGetLastError());
-  BCHK(hipEventRecord(g2dec, side));
+  HIPCHK_TO(err, hipGetLastError());
+  HIPCHK_TO(err, hipEventRecord(g2dec, side));
   hipLaunchKernelGGL(k_pghr_blines, dim3(nb), dim3(64), 0, side, (int)n, ddec, dokb, dbl);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   // one-wave blocks: a multi-wave block must find all its waves' registers on one CU, and beside the
   // side stream's ~280-register G2 waves it waited for them to finish (the 576-lane combs: 1.4 ->
   // 10.5 ms, profiles/r03s3_pghr_timeline.txt)
   hipLaunchKernelGGL(k_pghr_decode_g1, dim3(nb, 7), dim3(64), 0, st, (int)n, dp, ddec, dokb);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   hipLaunchKernelGGL(k_pghr_accp, dim3(nb, 9), dim3(64), 0, st, (int)n, din, dni, d->vk, d->comb, daccp);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   hipLaunchKernelGGL(k_pghr_prep, dim3(nb), dim3(64), 0, st, (int)n, din, dni, d->vk, dokb, daccp, ddec, dst);
-  BCHK(hipGetLastError());
-  BCHK(hipStreamWaitEvent(st, g2dec, 0));  // the final statuses (b's decode verdict joins)
+  HIPCHK_TO(err, hipGetLastError());
+  HIPCHK_TO(err, hipStreamWaitEvent(st, g2dec, 0));  // the final statuses (b's decode verdict joins)
   hipLaunchKernelGGL(k_pghr_g2status, dim3(nb), dim3(64), 0, st, (int)n, dokb, dst);
   // the b pairs' operands P_i7 (one GLV product + combs per proof): on the side stream after the b
   // lines from 32k proofs, where the main stream's Straus sums are the longer chain; below, the side
   // stream's G2 chain (128 waves of decodes and lines at 8k) is, and P_i7 follows the sums on main
   const bool p7_side = p7_on_side != 0;
   if (p7_side) {
-    BCHK(hipEventRecord(stready, st));
-    BCHK(hipStreamWaitEvent(side, stready, 0));
+    HIPCHK_TO(err, hipEventRecord(stready, st));
+    HIPCHK_TO(err, hipStreamWaitEvent(side, stready, 0));
     hipLaunchKernelGGL(k_pghr_p7, dim3(nb), dim3(64), 0, side, (int)n, ddec, drho, d->comb, dst, dpts);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
   }
-  BCHK(hipEventRecord(g2join, side));
+  HIPCHK_TO(err, hipEventRecord(g2join, side));
   // the six key pairs' operand sums (Straus over the GLV halves, B proofs per lane), concurrent with
   // the side stream's b lines and P_i7
   const long long G = ((long long)n + B - 1) / B;
@@ -1199,74 +1181,75 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
     hipLaunchKernelGGL(k_pghr_straus<2>, sg, dim3(64), 0, st, (int)n, ddec, drho, dst, dstr);
   else
     hipLaunchKernelGGL(k_pghr_straus<1>, sg, dim3(64), 0, st, (int)n, ddec, drho, dst, dstr);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   const unsigned nch = (unsigned)((4 * G + ZG_PGHR_SSUM_CH - 1) / ZG_PGHR_SSUM_CH);
   hipLaunchKernelGGL(k_pghr_ssum, dim3(ZG_BN_FIXED_Q, nch), dim3(64), 0, st, (int)G, dstr, dpart);
   hipLaunchKernelGGL(k_pghr_bsum_final, dim3(ZG_BN_FIXED_Q), dim3(64), 0, st, (int)nch, dpart, dagg);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   if (!p7_side) {
     hipLaunchKernelGGL(k_pghr_p7, dim3(nb), dim3(64), 0, st, (int)n, ddec, drho, d->comb, dst, dpts);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
   }
   // the batch check: every pair of the batch by loop segment (k_pghr_bseg: the key pairs on the sums
   // in block 0, the b pairs from the side stream's lines) and one product tree per segment ->
   // dseg[0..S); the easy part of the S values, their Horner product and ONE hard part
-  BCHK(hipMemsetAsync(dbst, ZG_STATUS_OK, ZG_PGHR_FSEG + 1, st));
-  BCHK(hipStreamWaitEvent(st, g2join, 0));
+  HIPCHK_TO(err, hipMemsetAsync(dbst, ZG_STATUS_OK, ZG_PGHR_FSEG + 1, st));
+  HIPCHK_TO(err, hipStreamWaitEvent(st, g2join, 0));
   const unsigned gb = 1 + bn_blocks(((long long)n + K - 1) / K);  // + the key pairs' block
   hipLaunchKernelGGL(k_pghr_bseg, dim3(gb, ZG_PGHR_FSEG), dim3(64), 0, st, (int)n, K, dpts, dst, dbl, dagg, d->lines,
                      dbseg);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   const size_t stride = gb;  // tree h over dbseg[h gb ..), dbtmp[h gb ..)
   Bq12 *src = dbseg, *dstb = dbtmp;
   for (int m = (int)gb; m > 1; m = (m + 1) / 2) {
     hipLaunchKernelGGL(k_bn_tree, dim3(bn_blocks((m + 1) / 2), ZG_PGHR_FSEG), dim3(64), 0, st, src, dstb, m, stride);
     std::swap(src, dstb);
   }
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   hipLaunchKernelGGL(k_pghr_segcopy, dim3(1), dim3(64), 0, st, dseg, src, stride);
   hipLaunchKernelGGL(k_fe_easy, dim3(1), dim3(64), 0, st, ZG_PGHR_FSEG + 1, dseg, dbst, dbw, 1);
   hipLaunchKernelGGL(k_pghr_fe_coop, dim3(1), dim3(64), 0, st, dbw, dbst);
-  BCHK(hipGetLastError());
+  HIPCHK_TO(err, hipGetLastError());
   uint8_t bok = 0;
-  BCHK(hipMemcpyAsync(&bok, dbst, 1, hipMemcpyDeviceToHost, st));
-  BCHK(hipStreamSynchronize(st));
+  HIPCHK_TO(err, hipMemcpyAsync(&bok, dbst, 1, hipMemcpyDeviceToHost, st));
+  HIPCHK_TO(err, hipStreamSynchronize(st));
   if (batch_failed) *batch_failed = bok != ZG_STATUS_OK;
   if (bok != ZG_STATUS_OK) {  // some proof fails: the per-proof path for the exact statuses
     hipLaunchKernelGGL(k_pghr_rho, dim3(nb), dim3(64 * ZG_PGHR_NMUL), 0, st, (int)n, ddec, drho, dst, dmul);
     hipLaunchKernelGGL(k_pghr_combine, dim3(nb), dim3(64), 0, st, (int)n, ddec, dmul, drho, d->comb, dst, dpts);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_pghr_miller, dim3(nb), dim3(64 * halves), 0, st, (int)n, dpts, d->lines, dst, df, halves);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_fe_easy, dim3(nb), dim3(64), 0, st, (int)n, df, dst, dw, halves);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_fe_exp<1>, dim3(nb), dim3(64), 0, st, (int)n, dst, dw);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_fe_exp<2>, dim3(nb), dim3(64), 0, st, (int)n, dst, dw);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_fe_exp<3>, dim3(nb), dim3(64), 0, st, (int)n, dst, dw);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
     hipLaunchKernelGGL(k_fe_last, dim3(nb), dim3(64), 0, st, (int)n, dst, dw);
-    BCHK(hipGetLastError());
+    HIPCHK_TO(err, hipGetLastError());
   }
-  if (kernel_ms) BCHK(hipEventRecord(e1, st));
-  BCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
-  BCHK(hipStreamSynchronize(st));
-  if (kernel_ms) BCHK(hipEventElapsedTime(kernel_ms, e0, e1));
+  if (kernel_ms) HIPCHK_TO(err, hipEventRecord(e1, st));
+  HIPCHK_TO(err, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
+  HIPCHK_TO(err, hipStreamSynchronize(st));
+  if (kernel_ms) HIPCHK_TO(err, hipEventElapsedTime(kernel_ms, e0, e1));
   return ZG_OK;
 }
 
 int bn_pairing(hipStream_t st, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, std::string* err) {
   if (!n) return ZG_OK;
+  DevScratch s;
   uint32_t *a = nullptr, *b = nullptr, *o = nullptr;
   Bq12 *f = nullptr, *w = nullptr;
   uint8_t* ok = nullptr;
-  hipError_t e = hipMalloc(&a, 64 * n);
-  if (e == hipSuccess) e = hipMalloc(&b, 128 * n);
-  if (e == hipSuccess) e = hipMalloc(&o, 384 * n);
-  if (e == hipSuccess) e = hipMalloc(&f, sizeof(Bq12) * n);
-  if (e == hipSuccess) e = hipMalloc(&w, sizeof(Bq12) * ZG_FE_SLOTS * n);
-  if (e == hipSuccess) e = hipMalloc(&ok, n);
+  hipError_t e = s.alloc(&a, 64 * n);
+  if (e == hipSuccess) e = s.alloc(&b, 128 * n);
+  if (e == hipSuccess) e = s.alloc(&o, 384 * n);
+  if (e == hipSuccess) e = s.alloc(&f, sizeof(Bq12) * n);
+  if (e == hipSuccess) e = s.alloc(&w, sizeof(Bq12) * ZG_FE_SLOTS * n);
+  if (e == hipSuccess) e = s.alloc(&ok, n);
   if (e == hipSuccess) e = hipMemsetAsync(ok, ZG_STATUS_OK, n, st);
   if (e == hipSuccess) e = hipMemcpyAsync(a, g1, 64 * n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(b, g2, 128 * n, hipMemcpyHostToDevice, st);
@@ -1282,8 +1265,6 @@ int bn_pairing(hipStream_t st, size_t n, const uint8_t* g1, const uint8_t* g2, u
   }
   if (e == hipSuccess) e = hipMemcpyAsync(gt, o, 384 * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  for (void* q : {(void*)a, (void*)b, (void*)o, (void*)f, (void*)w, (void*)ok})
-    if (q) hipFree(q);
   if (e != hipSuccess) {
     *err = std::string("zg_bn254_pairing: ") + hipGetErrorString(e);
     return ZG_E_HIP;
