@@ -135,6 +135,4 @@ def test_lazy_operand_forms():
     the products' ZG_KIND codes, interpreted on extreme (0, p - 1) and random atoms: every carry
     chain stays within [0, 2^384), operands equal the forms mod p, outputs are canonical, and the
     raw product bounds fit the conditional subtractions / quotient estimate the code selects"""
-    if not gen_prog.LAZY:
-        return
     gen_prog.check_lazy(gen_prog.build_all(), trials=12)

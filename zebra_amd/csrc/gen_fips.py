@@ -1,14 +1,10 @@
 #!/usr/bin/env python3
-"""Generate zg_fips.h: the gfx950 Montgomery product for Fq (12 x 32-bit limbs), Finely
-Integrated Product Scanning, as one inline-asm statement per column group. Build tooling.
+"""Generate zg_fips.h: the Fq / Fq2 add and sub forms of gfx950 (12 x 32-bit limbs), each a few
+VALU carry chains in one inline-asm statement. Build tooling.
 
-Every 32x32 product is one v_mad_u64_u32 into the 64-bit {lo, mid} column accumulator; its
-carry-out (an SGPR-pair lane mask) feeds one v_addc_co_u32 into the high word. hipcc pads
-every inline-asm statement boundary with a wait state, so the round-1 form (one statement per
-instruction) paid ~250 s_nop per product. Here a whole column is one statement and the carry
-masks alternate between two SGPR pairs so that each v_addc_co_u32 sits one instruction after
-the v_mad_u64_u32 whose carry it consumes (the same one-state spacing the round-1 form had
-from the boundary pad):  mad_1 mad_2 addc_1 mad_3 addc_2 ... mad_n addc_(n-1) addc_n.
+hipcc pads every inline-asm statement boundary with a wait state, and an instruction that reads a
+carry mask (an SGPR pair) must not directly follow the one that writes it. So a whole form is one
+statement and its independent chains are interleaved (schedule_chains below).
 
     python zebra_amd/csrc/gen_fips.py > zebra_amd/csrc/zg_fips.h
 """
@@ -17,39 +13,11 @@ import sys
 N = 12
 
 
-def column(prods, tag):
-    """asm statement accumulating prods = [(x_operand, y_operand)] into (lm, h)."""
-    ins = []
-    opnames = {}
-
-    def op(expr, cons):
-        if expr not in opnames:
-            opnames[expr] = "%s%d" % (cons[0] if cons != "s" else "k", len(opnames))
-            ins.append((opnames[expr], cons, expr))
-        return "%[" + opnames[expr] + "]"
-    text = []
-    n = len(prods)
-    for k, (x, y) in enumerate(prods):
-        c = "%[c0]" if k % 2 == 0 else "%[c1]"
-        text.append("v_mad_u64_u32 %%[lm], %s, %s, %s, %%[lm]" % (c, op(x, "v"), op(y, "s" if y.startswith(("FQ_P", "FR_R", "BQ_P")) else "v")))
-        if k >= 1:
-            cp = "%[c0]" if (k - 1) % 2 == 0 else "%[c1]"
-            text.append("v_addc_co_u32 %%[h], vcc, 0, %%[h], %s" % cp)
-    if n == 1:
-        text.append("s_nop 0")
-    cl = "%[c0]" if (n - 1) % 2 == 0 else "%[c1]"
-    text.append("v_addc_co_u32 %%[h], vcc, 0, %%[h], %s" % cl)
-    body = "\\n\\t".join(text)
-    inputs = ", ".join('[%s] "%s"(%s)' % (nm, cons, expr) for nm, cons, expr in ins)
-    return ('  asm volatile("%s"\n               : [lm] "+v"(lm), [h] "+v"(h), [c0] "=&s"(c0), [c1] "=&s"(c1)\n'
-            '               : %s\n               : "vcc");  // %s' % (body, inputs, tag))
-
-
 # ---------------------------------------------------------------- add / sub carry chains
 # An Fq op is a few carry chains over 12 limbs plus per-limb selects. Instructions:
 #   (text, reads_carry, writes_carry, chain_id, seq)   operands as %[name]
 # The scheduler interleaves the chains of one statement so that no instruction reads a carry
-# mask written by the instruction right before it (one wait state, as above), inserting
+# mask written by the instruction right before it (one wait state), inserting
 # s_nop 0 only when nothing else is ready.
 def op_add(tag, r, a, b):
     """r = (a + b) mod p: s = a + b ; d = s - p ; r = borrow ? s : d"""
@@ -95,20 +63,6 @@ def op_lzadd(tag, r, a, b):
     return ins, [], [tag + "k0"]
 
 
-def op_lzsub(tag, r, a, b):
-    """r = a + (p - b) (no reduction)"""
-    ins = []
-    for i in range(N):
-        x = "v_sub_co_u32 %%[%sd%d], %%[%sk0], %%[p%d], %s" % (tag, i, tag, i, b(i)) if i == 0 else \
-            "v_subb_co_u32 %%[%sd%d], %%[%sk0], %%[p%d], %s, %%[%sk0]" % (tag, i, tag, i, b(i), tag)
-        ins.append((x, None if i == 0 else tag + "k0", tag + "k0", tag + "A", i, []))
-    for i in range(N):
-        x = "v_add_co_u32 %s, %%[%sk1], %s, %%[%sd%d]" % (r(i), tag, a(i), tag, i) if i == 0 else \
-            "v_addc_co_u32 %s, %%[%sk1], %s, %%[%sd%d], %%[%sk1]" % (r(i), tag, a(i), tag, i, tag)
-        ins.append((x, None if i == 0 else tag + "k1", tag + "k1", tag + "B", i, []))
-    return ins, ["%sd%d" % (tag, i) for i in range(N)], [tag + "k0", tag + "k1"]
-
-
 def op_psub(tag, r, a, b):
     """r = a - b (no reduction; the caller guarantees a >= b)"""
     ins = []
@@ -119,7 +73,7 @@ def op_psub(tag, r, a, b):
     return ins, [], [tag + "k0"]
 
 
-OPS = {"add": op_add, "sub": op_sub, "lzadd": op_lzadd, "lzsub": op_lzsub, "psub": op_psub}
+OPS = {"add": op_add, "sub": op_sub, "lzadd": op_lzadd, "psub": op_psub}
 
 
 def schedule_chains(ops):
@@ -190,95 +144,16 @@ def fq_ops_fn(name, kinds):
     return lines
 
 
-FQ_FNS = [("fqa_add", ["add"]), ("fqa_sub", ["sub"]), ("fqa_lzadd", ["lzadd"]), ("fqa_lzsub", ["lzsub"]),
+FQ_FNS = [("fqa_add", ["add"]), ("fqa_sub", ["sub"]), ("fqa_lzadd", ["lzadd"]),
           ("f2a_add", ["add", "add"]), ("f2a_sub", ["sub", "sub"]), ("f2a_lzadd", ["lzadd", "lzadd"]),
-          ("f2a_lzsub", ["lzsub", "lzsub"]), ("f2a_sub_add", ["sub", "add"]), ("f2a_lzadd_lzsub", ["lzadd", "lzsub"]),
+          ("f2a_sub_add", ["sub", "add"]),
           # plain (unreduced) accumulation steps of the staged engine's lazy operand forms
           ("f2p_as", ["lzadd", "psub"]), ("f2p_sa", ["psub", "lzadd"]), ("f2p_ss", ["psub", "psub"]), ("fqp_sub", ["psub"])]
 
 
-def gen_mul(name, n, pname, inv, rinv, bound, tbound):
-    """the FIPS Montgomery product over n limbs (modulus pname, -p^-1 mod 2^32 = inv)"""
-    out = ["// r = a * b * %s mod p ; a * b < 2^%d p (e.g. %s)  ->  r < p" % (rinv, 32 * n, bound),
-           "__device__ __forceinline__ void %s(uint32_t* r, const uint32_t* a, const uint32_t* b) {" % name,
-           "  uint32_t m[%d], t[%d];" % (n, n), "  uint64_t lm = 0, c0, c1;", "  uint32_t h = 0;"]
-    for i in range(n):
-        prods = [("a[%d]" % j, "b[%d]" % (i - j)) for j in range(i + 1)]
-        prods += [("m[%d]" % j, "%s[%d]" % (pname, i - j)) for j in range(i)]
-        out.append(column(prods, "column %d: a b and m p products" % i))
-        out.append("  m[%d] = (uint32_t)lm * %s;" % (i, inv))
-        out.append(column([("m[%d]" % i, "%s[0]" % pname)], "column %d: m_%d p_0" % (i, i)))
-        out.append("  lm = (lm >> 32) | ((uint64_t)h << 32);")
-        out.append("  h = 0;")
-    for i in range(n, 2 * n - 1):
-        prods = [("a[%d]" % j, "b[%d]" % (i - j)) for j in range(i - n + 1, n)]
-        prods += [("m[%d]" % j, "%s[%d]" % (pname, i - j)) for j in range(i - n + 1, n)]
-        out.append(column(prods, "column %d" % i))
-        out.append("  t[%d] = (uint32_t)lm;" % (i - n))
-        out.append("  lm = (lm >> 32) | ((uint64_t)h << 32);")
-        out.append("  h = 0;")
-    out.append("  t[%d] = (uint32_t)lm;  // %s: no further carry" % (n - 1, tbound))
-    out.append("  uint32_t pm[%d];" % n)
-    out.append("#pragma unroll")
-    out.append("  for (int i = 0; i < %d; i++) pm[i] = %s[i];" % (n, pname))
-    out.append("  mp_reduce_once<%d>(r, t, pm);" % n)
-    out.append("}")
-    return out
-
-
 def main():
     out = ["// GENERATED by zebra_amd/csrc/gen_fips.py -- do not edit.", "#pragma once"]
-    out += gen_mul("fq_mul_fips", 12, "FQ_P", "FQ_INV", "2^-384", "a < 4p, b < 2p", "< 2p < 2^382")
-    out.append("")
-    # Fr (the Jubjub base field): a, b < r < 2^255, so a b < 2^256 r and t < 2r < 2^256
-    out += gen_mul("fr_mul_fips", 8, "FR_R", "FR_INV", "2^-256", "a, b < r", "< 2r < 2^256")
-    out.append("")
-    # BN254 Fq (PGHR13): a, b < p < 2^254
-    out += gen_mul("bq_mul_fips", 8, "BQ_P", "BQ_INV", "2^-256", "a, b < p", "< 2p < 2^255")
-    out.append("")
-    # ---- lazy-reduction building blocks: the 24-limb product and the Montgomery reduction of a
-    # 24-limb value, the same column statements split in two (an Fq2 Karatsuba product reduces
-    # twice instead of three times: zg_prog.h f2_mul_kind)
-    out += ["// t = a * b (24 limbs, no reduction)",
-            "__device__ __forceinline__ void fq_mul_wide(uint32_t* t, const uint32_t* a, const uint32_t* b) {",
-            "  uint64_t lm = 0, c0, c1;", "  uint32_t h = 0;"]
-    for i in range(2 * N - 1):
-        prods = [("a[%d]" % j, "b[%d]" % (i - j)) for j in range(max(0, i - N + 1), min(i, N - 1) + 1)]
-        out.append(column(prods, "column %d" % i))
-        out.append("  t[%d] = (uint32_t)lm;" % i)
-        out.append("  lm = (lm >> 32) | ((uint64_t)h << 32);")
-        out.append("  h = 0;")
-    out.append("  t[%d] = (uint32_t)lm;" % (2 * N - 1))
-    out.append("}")
-    out.append("")
-    out += ["// r = t * 2^-384 mod p for t < 2^384 p (24 limbs)  ->  r < p",
-            "__device__ __forceinline__ void fq_redc_wide(uint32_t* r, const uint32_t* t) {",
-            "  uint32_t m[12], u[12];", "  uint64_t lm = 0, c0, c1;", "  uint32_t h = 0;"]
-    for i in range(N):
-        out.append("  lm += t[%d];  // lm < 2^38 here: no overflow" % i)
-        prods = [("m[%d]" % j, "FQ_P[%d]" % (i - j)) for j in range(i)]
-        if prods:
-            out.append(column(prods, "column %d: m p products" % i))
-        out.append("  m[%d] = (uint32_t)lm * FQ_INV;" % i)
-        out.append(column([("m[%d]" % i, "FQ_P[0]")], "column %d: m_%d p_0" % (i, i)))
-        out.append("  lm = (lm >> 32) | ((uint64_t)h << 32);")
-        out.append("  h = 0;")
-    for i in range(N, 2 * N - 1):
-        out.append("  lm += t[%d];" % i)
-        prods = [("m[%d]" % j, "FQ_P[%d]" % (i - j)) for j in range(i - N + 1, N)]
-        out.append(column(prods, "column %d" % i))
-        out.append("  u[%d] = (uint32_t)lm;" % (i - N))
-        out.append("  lm = (lm >> 32) | ((uint64_t)h << 32);")
-        out.append("  h = 0;")
-    out.append("  lm += t[%d];" % (2 * N - 1))
-    out.append("  u[11] = (uint32_t)lm;  // < 2p < 2^382: no further carry")
-    out.append("  uint32_t pm[12];")
-    out.append("#pragma unroll")
-    out.append("  for (int i = 0; i < 12; i++) pm[i] = FQ_P[i];")
-    out.append("  mp_reduce_once<12>(r, u, pm);")
-    out.append("}")
-    out.append("")
-    out.append("// ---- Fq add / sub carry chains, one asm statement each (interleaved chains, see above)")
+    out.append("// ---- Fq add / sub carry chains, one asm statement each (interleaved chains)")
     for name, kinds in FQ_FNS:
         out += fq_ops_fn(name, kinds)
     sys.stdout.write("\n".join(out) + "\n")

@@ -5,7 +5,7 @@ Storage stays 12 x 32-bit words in Montgomery form R = 2^384. A product splits i
 into 14 digits of 29 bits (v_alignbit + v_and), so every digit product is < 2^58 and a whole
 column -- up to 56 a*b, a'*b' and m*p terms -- fits one 64-bit accumulator: ONE carry-free
 v_mad_u64_u32 per digit product, against v_mad_u64_u32 + v_addc_co_u32 per 32x32 product in
-the word form (gen_fips.py). The reduction is finely integrated (FIPS) and mixed-radix: 13
+a 32-bit-word product scan. The reduction is finely integrated (FIPS) and mixed-radix: 13
 digits of 29 bits and a last one of 7 bits divide by exactly 2^384 (377 + 7); the 7-bit tail
 is absorbed by the bit offsets of the final repacking into 32-bit words.
 

@@ -348,25 +348,6 @@ def prog_aq4():
 PROD_CLK = {K_MUL: 8600, K_SQR: 6500, K_MULC0: 6500, K_MULC1: 6500}
 
 
-def _form_instr(f, lazy):
-    terms = list(f.values())
-    if len(terms) == 1 and terms[0] == (1, 0):
-        return 0
-    if lazy and len(terms) == 2 and all(t == (1, 0) for t in terms):
-        return 24
-    n = 0
-    for c0, c1 in terms:
-        if (c0, c1) in ((1, 0), (-1, 0)):
-            pass
-        elif (c0, c1) in ((1, 1), (-1, -1)) or c1 == 0 and abs(c0) == 2:
-            n += 74
-        elif (c0, c1) in ((0, 1), (0, -1)):
-            n += 25
-        else:
-            n += 74 * 3
-    return n + 74 * (len(terms) - 1)
-
-
 def _lazy_cost(lines, code):
     n = 0
     for ln in lines:
@@ -382,17 +363,12 @@ def _lazy_cost(lines, code):
 
 def prod_costs(prog):
     out = []
-    if LAZY:
-        slot = {}  # costs do not depend on the slot map
-        for k in {k for L, R, _ in prog.prods for k in list(L) + list(R)}:
-            slot[k] = ("g", 0) if k[0] == "in" and k[1] in prog.glob else 0
-        for L, R, kind in prog.prods:
-            lines, code = lazy_product(L, R, kind, slot)
-            out.append(PROD_CLK[kind] + 4.4 * _lazy_cost(lines, code))
-        return out
+    slot = {}  # costs do not depend on the slot map
+    for k in {k for L, R, _ in prog.prods for k in list(L) + list(R)}:
+        slot[k] = ("g", 0) if k[0] == "in" and k[1] in prog.glob else 0
     for L, R, kind in prog.prods:
-        c = _form_instr(L, True) + (0 if kind == K_SQR else _form_instr(R, False))
-        out.append(PROD_CLK[kind] + 4.4 * c)
+        lines, code = lazy_product(L, R, kind, slot)
+        out.append(PROD_CLK[kind] + 4.4 * _lazy_cost(lines, code))
     return out
 
 
@@ -586,35 +562,6 @@ def reference(prog, outs, vals):
 
 
 # ---------------------------------------------------------------- code generation
-def scaled(s, c0, c1):
-    """(C++ expression, sign) of (c0 + c1 u) * atom-in-slot-s"""
-    x = "at.q(%d)" % s[1] if isinstance(s, tuple) else "at.get(%d)" % s
-    if (c0, c1) in ((1, 0), (-1, 0)):
-        return x, c0
-    if (c0, c1) in ((1, 1), (-1, -1)):
-        return "f2_mul_nr(%s)" % x, c0
-    if (c0, c1) in ((0, 1), (0, -1)):
-        return "f2_mul_u(%s)" % x, c1
-    if c1 == 0:
-        return "f2_smul<%d>(%s)" % (abs(c0), x), 1 if c0 > 0 else -1
-    return "f2_gmul<%d, %d>(%s)" % (c0, c1, x), 1
-
-
-def form_code(f, slot, lazy):
-    """C++ expression for a form. lazy: the value feeds a product as its lazy operand, so a
-    plain sum / difference of two canonical atoms may skip the reduction (< 2p)."""
-    order = lambda kv: (1, slot[kv[0]][1]) if isinstance(slot[kv[0]], tuple) else (0, slot[kv[0]])
-    terms = [scaled(slot[k], c0, c1) for k, (c0, c1) in sorted(f.items(), key=order)]
-    terms.sort(key=lambda t: -t[1])  # a positive term first
-    if lazy and len(terms) == 2 and all(t[0].startswith(("at.get", "at.q")) for t in terms) and terms[0][1] > 0:
-        return "f2_lz_%s(%s, %s)" % ("add" if terms[1][1] > 0 else "sub", terms[0][0], terms[1][0])
-    e, sg = terms[0]
-    acc = e if sg > 0 else "f2_neg(%s)" % e
-    for e, sg in terms[1:]:
-        acc = "f2_%s(%s, %s)" % ("add" if sg > 0 else "sub", acc, e)
-    return acc
-
-
 # ---------------------------------------------------------------- lazy operand forms
 # An operand coefficient is evaluated as a plain 12-word integer: the K p offset that covers its
 # negative terms, plus / minus atom coefficients one unit at a time (f2a_lzadd / f2p_* dual carry
@@ -622,7 +569,6 @@ def form_code(f, slot, lazy):
 # (<= 9 so that it stays below 2^384); a longer form is reduced mid-way (fq_reduce_q). The product
 # gets ZG_KIND(kind, k, red) from the bounds: red conditional subtractions (or 0: fq_reduce_q)
 # bring its raw result t < S / 2^384 + p, S <= M p^2, back below p.
-LAZY = True
 SEG_FIRST, SEG_NEXT = 9, 8
 KMAX = 12
 
@@ -912,40 +858,20 @@ def emit(specs):
         # products
         for i, (L, R, kind) in enumerate(prog.prods):
             s = sch["slot"]
-            if LAZY:
-                d = s[("p", i)]
-                dst = SINK_BASE + d[1] if isinstance(d, tuple) else d
-                lines, code = lazy_product(L, R, kind, s)
-                prod_cases.append("  case %d: %s {  // %s p%d round %d%s\n    %s\n    dst = %d; return %s;\n  } break;" % (
-                    gk + i, use, name, i, sch["rnd"][i], " -> HBM output %d" % d[1] if isinstance(d, tuple) else "",
-                    "\n    ".join(lines), dst, code))
-                continue
-            if kind == K_SQR:
-                x, y = form_code(L, s, False), "x"
-            elif kind in (K_MULC0, K_MULC1):
-                x, y = form_code(L, s, True), form_code(R, s, False)
-            else:
-                # at most one lazy operand: the one that is a plain two-term sum
-                lx = form_code(L, s, True)
-                if lx.startswith("f2_lz_"):
-                    x, y = lx, form_code(R, s, False)
-                else:
-                    x, y = form_code(R, s, True), form_code(L, s, False)
             d = s[("p", i)]
             dst = SINK_BASE + d[1] if isinstance(d, tuple) else d
-            prod_cases.append("  case %d: %s { x = %s; y = %s; dst = %d; return %d; } break;  // %s p%d round %d%s" % (
-                gk + i, use, x, y, dst, kind, name, i, sch["rnd"][i], " -> HBM output %d" % d[1] if isinstance(d, tuple) else ""))
+            lines, code = lazy_product(L, R, kind, s)
+            prod_cases.append("  case %d: %s {  // %s p%d round %d%s\n    %s\n    dst = %d; return %s;\n  } break;" % (
+                gk + i, use, name, i, sch["rnd"][i], " -> HBM output %d" % d[1] if isinstance(d, tuple) else "",
+                "\n    ".join(lines), dst, code))
         for j, f in enumerate(outs):
             if j in sch.get("sinks", {}).values():
                 out_cases.append("  case %d: return f2_zero();  // %s out %d: stored by its product" % (go + j, name, j))
-            elif LAZY:
+            else:
                 lines, _ = lazy_form(f, sch["slot"], "v", True)
                 lines = hoist_loads(lines)
                 out_cases.append("  case %d: %s {  // %s out %d\n    Fq2 v;\n    %s\n    return v;\n  } break;" % (
                     go + j, use, name, j, "\n    ".join(lines)))
-            else:
-                out_cases.append("  case %d: %s { return %s; } break;  // %s out %d" % (
-                    go + j, use, form_code(f, sch["slot"], False), name, j))
         off = len(sched)
         for pick in sch["rounds"]:
             sched.extend([-1 if i is None else i for i in pick] + [-1] * (nw - len(pick)))
@@ -953,7 +879,6 @@ def emit(specs):
                       sch["rb"]))
         gk += len(prog.prods)
         go += len(outs)
-    out.append("#define ZG_PROG_LAZY %d  // operands as lazy forms, products return ZG_KIND codes" % int(LAZY))
     out.append("struct ProgInfo { int nin, nprod, nout, nrounds, nw, sched, gk, go, nslots, rb; };")
     for k, (name, nin, npr, nout, nr, nw, off, g1, g2, ns, rb) in enumerate(infos):
         out.append("#define ZG_PROG_%s %d  // %d products in %d rounds of %d waves, %d LDS slots%s" % (
@@ -1063,8 +988,7 @@ if __name__ == "__main__":
         json.dump({name: sch["rounds"] for name, prog, outs, nw, sch in specs if name in SEARCH},
                   open(SCHED_CACHE, "w"), indent=0)
     selfcheck(specs)
-    if LAZY:
-        check_lazy(specs)
+    check_lazy(specs)
     for name, prog, outs, nw, sch in specs:
         sys.stderr.write("%s: %d products, rounds %s (nw %d), %d slots\n" % (
             name, len(prog.prods), [sum(i is not None for i in r) for r in sch["rounds"]], nw, sch["nslots"]))

@@ -1,8 +1,8 @@
 // zg_bn254.h -- BN254 ("alt_bn128", the `bn` crate) on gfx950 for PGHR13 Sprout proofs
 // (crypto/src/pghr13.rs). One lane per proof.
 //
-//   Fq      8 x 32-bit limbs, Montgomery R = 2^256; products by the product-scanning FIPS
-//           Montgomery multiply (zg_fips.h bq_mul_fips), out of line to keep kernels small
+//   Fq      8 x 32-bit limbs, Montgomery R = 2^256; products in 29-bit digits (zg_fq29_gen.h
+//           bq29_mul), out of line to keep kernels small
 //   tower   Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v), xi = 9 + u;
 //           an Fq12 element A + B w holds the coefficients of w^0, w^2, w^4 (A) and w^1, w^3, w^5
 //           (B) of the oracle's Fq2[w]/(w^6 - xi) form (oracle/bn254.py)
@@ -43,13 +43,7 @@ ZG_NOINL inline u32x8 bq_mul_v(u32x8 a0, u32x8 b0) {
     a.l[i] = a0[i];
     b.l[i] = b0[i];
   }
-#if ZG_FQ29
   bq29_mul(r.l, a.l, b.l);  // 29-bit digits (zg_fq29_gen.h; host: same code)
-#elif defined(__HIP_DEVICE_COMPILE__)
-  bq_mul_fips(r.l, a.l, b.l);
-#else
-  r = fp_mul_inl<BqM>(a, b);
-#endif
   u32x8 o;
 #pragma unroll
   for (int i = 0; i < 8; i++) o[i] = r.l[i];

@@ -4,7 +4,7 @@
 // change representation: operands are split into 14 digits of 29 bits, so a digit product is
 // < 2^58 and a whole column of up to 56 of them (a*b, a'*b' and m*p terms) fits one 64-bit
 // accumulator. Each digit product is ONE v_mad_u64_u32 with no carry handling, against a
-// v_mad_u64_u32 plus a v_addc_co_u32 per 32 x 32 product in the word form (zg_fips.h).
+// v_mad_u64_u32 plus a v_addc_co_u32 per 32 x 32 product in a 32-bit-word product scan.
 // The reduction divides by exactly 2^384 with mixed-radix digits (13 x 29 bits + 7 bits).
 //
 //   fq29_mul   a b             (392 digit products)

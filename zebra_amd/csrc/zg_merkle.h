@@ -33,23 +33,14 @@ namespace zg {
 #define ZG_PH_POINTS (ZG_PH_GENS * ZG_PH_WIN * ZG_PH_CODES)
 #define ZG_PH_TABLE_BYTES ((size_t)ZG_PH_POINTS * ZG_PH_WORDS * 4)
 
-// The Pedersen additions multiply with the inlined product-scanning Montgomery product
-// (fr29_mul: 29-bit digits, one carry-free v_mad_u64_u32 per digit product; round 1: fr_mul_fips)
-// rather than the out-of-line fr_mul call: a hash
-// group is a lone wave on a latency-bound chain of tree levels, so its time is the number of
-// instructions it issues.
+// The Pedersen additions multiply with the digit product inlined (fr29_mul, zg_fq29_gen.h: 29-bit
+// digits, one carry-free v_mad_u64_u32 per digit product) rather than through the out-of-line
+// fr_mul call: a hash group is a lone wave on a latency-bound chain of tree levels, so its time is
+// the number of instructions it issues.
 ZG_INL Fr ph_mul(const Fr& a, const Fr& b) {
-#if ZG_FQ29
   Fr r;
-  fr29_mul(r.l, a.l, b.l);  // 29-bit digits, one carry-free v_mad_u64_u32 per digit product (zg_fq29_gen.h)
+  fr29_mul(r.l, a.l, b.l);
   return r;
-#elif defined(__HIP_DEVICE_COMPILE__)
-  Fr r;
-  fr_mul_fips(r.l, a.l, b.l);  // gfx950: v_mad_u64_u32 carry-out product scanning (zg_fips.h)
-  return r;
-#else
-  return fp_mul_inl<FrM>(a, b);
-#endif
 }
 
 // add-2008-hwcd-3 (a = -1, k = 2d), q given as a niels point (affine): 7 multiplications
