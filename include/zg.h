@@ -348,6 +348,69 @@ int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_o
                const uint32_t* script_off, const uint64_t* amount, const uint32_t* hashtype, uint8_t* tx_status,
                uint8_t* hashes, uint8_t* status);
 
+/* ---- pay-to-pubkey-hash and pay-to-pubkey inputs on the GPU: for the two templates
+ * that make up nearly every transparent input, the whole of verify_script -- the byte match, HASH160, the
+ * BIP66 encoding check, the signature hash and the ECDSA check -- from the serialized transactions and the
+ * spent outputs' scripts, with one upload and one download of statuses. The interpreter stays on the host:
+ * any other input is reported ZG_INPUT_HOST and the caller runs verify_script on it as before. Device memory
+ * per call, n = 0 / ntx = 0, the transaction arena, the offset tables and the argument checks as zg_sighash.
+ *   zg_script_class <- the template matcher zg_inputs_verify runs per item. CPU, no context. Under the flags
+ *        of verification/src/accept_transaction.rs:334-358 (strictenc, nulldummy, sigpushonly, cleanstack off;
+ *        low_s, minimaldata off by default) eval_script (script/src/interpreter.rs:361-1120) of
+ *          ZG_SCRIPT_P2PKH  script_pubkey = 76 a9 14 <20 bytes> 88 ac, script_sig = two push instructions
+ *          ZG_SCRIPT_P2PK   script_pubkey = 21 <33 bytes> ac or 41 <65 bytes> ac (any key bytes),
+ *                           script_sig = one push instruction
+ *        reduces to the checks below. A push instruction: opcode 00 (the empty string), 01..4b or
+ *        OP_PUSHDATA1/2/4, the data wholly inside the script and at most 520 bytes; the instructions consume
+ *        script_sig entirely. OP_1NEGATE, OP_1..OP_16, any other opcode, a push past the end or over 520 bytes,
+ *        extra pushes: ZG_SCRIPT_HOST. out[0] the class, out[1..2] offset and length of the signature push in
+ *        script_sig, out[3..4] of the key push (P2PK: offset into script_pubkey); all zero for HOST.
+ *        ZG_E_INVAL for a null pointer with a non-zero length.
+ *   zg_inputs_verify <- verify_script (interpreter.rs:288-360) as TransactionEval::check calls it
+ *        (accept_transaction.rs:363-422) for item i = input input_index[i] of transaction item_tx[i] spending
+ *        an output of value amount[i] whose script is prev_scripts[prev_off[i] .. prev_off[i+1]) (n + 1
+ *        offsets, not decreasing). flags: ZG_SCRIPT_VERIFY_DERSIG or 0 (bip66_height is 0 on every network of
+ *        network/src/consensus.rs; any other bit is ZG_E_INVAL). The script code is the previous script byte
+ *        for byte (interpreter.rs:771: no find_and_delete, no code-separator subscript); the hashtype is the
+ *        signature push's last byte as a u32 (interpreter.rs:27). The checks run in the interpreter's order
+ *        and the first failing one is the status:
+ *          ZG_INPUT_EQUALVERIFY    P2PKH: dhash160 of the key push (any length 0..520; interpreter.rs:756-758,
+ *                                  crypto/src/lib.rs:158-166,202-206) is not the script's 20 bytes
+ *          ZG_INPUT_SIGNATURE_DER  DERSIG set, the signature push not empty and is_valid_signature_encoding
+ *                                  (interpreter.rs:49-136,159-180) false
+ *          ZG_INPUT_EVAL_FALSE     check_signature (interpreter.rs:12-31) false, so the script leaves a false
+ *                                  top: the key does not parse, the signature push is empty, from_der_lax
+ *                                  fails, or verify is false over signature_hash(Some(index), amount,
+ *                                  script_pubkey, hashtype, branch id)
+ *          ZG_INPUT_HOST           not a template: run verify_script
+ *          ZG_INPUT_TX_MALFORMED / _TX_NONCANONICAL  the item's transaction is (ZG_TX_*)
+ *          ZG_INPUT_RANGE          input_index >= inputs, for every transaction format
+ *        -> tx_status ntx (ZG_TX_*), status n, detail n (optional): for EVAL_FALSE the ZG_ECDSA_* status
+ *        zg_ecdsa_verify gives for that key and DER signature (the empty signature for an empty push), else 0;
+ *        hashes n x 32 (optional): the signature hash in H256 storage order where the reference computes one
+ *        (the earlier checks passed, the key is 33 or 65 bytes, the signature push not empty), else zero.
+ *        One kernel lane per template item reads the pushes in place, then the two kernels of zg_sighash and
+ *        the kernel of zg_ecdsa_verify run on device-resident data; HOST, RANGE and TX_* items launch nothing.
+ *        zg_last_sig_kernel_ms covers the kernels of this entry. */
+#define ZG_SCRIPT_HOST 0
+#define ZG_SCRIPT_P2PKH 1
+#define ZG_SCRIPT_P2PK 2
+#define ZG_SCRIPT_VERIFY_DERSIG 1
+#define ZG_INPUT_OK 0
+#define ZG_INPUT_EQUALVERIFY 1     /* Error::EqualVerify */
+#define ZG_INPUT_SIGNATURE_DER 2   /* Error::SignatureDer */
+#define ZG_INPUT_EVAL_FALSE 3      /* Error::EvalFalse */
+#define ZG_INPUT_HOST 4
+#define ZG_INPUT_TX_MALFORMED 5
+#define ZG_INPUT_TX_NONCANONICAL 6
+#define ZG_INPUT_RANGE 7
+int zg_script_class(const uint8_t* script_sig, size_t sig_len, const uint8_t* script_pubkey, size_t pk_len,
+                    uint64_t out[5]);
+int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
+                     size_t n, const uint32_t* item_tx, const uint32_t* input_index, const uint8_t* prev_scripts,
+                     const uint32_t* prev_off, const uint64_t* amount, uint32_t flags, uint8_t* tx_status,
+                     uint8_t* status, uint8_t* detail, uint8_t* hashes);
+
 /* ---- block bodies on the GPU: the transaction ids, the merkle root and the checks
  * of BlockVerifier::check, one call per import window. Device memory per call; n = 0 / nblk = 0 and the
  * argument checks as zg_headers_verify. zg_last_sig_kernel_ms covers the kernels of zg_txids and

@@ -27,7 +27,8 @@ use std::convert::TryInto;
 use std::sync::Arc;
 
 use super::cpu::CpuBackend;
-use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, Item, SighashItem};
+use super::{prep_joinsplit, prep_joinsplit_bn, prep_output, prep_spend, GpuError, GpuVerifier, InputItem, Item, SighashItem};
+use super::ffi::{ZG_INPUT_EQUALVERIFY, ZG_INPUT_EVAL_FALSE, ZG_INPUT_OK, ZG_INPUT_SIGNATURE_DER, ZG_SCRIPT_VERIFY_DERSIG};
 use super::ffi::{ZG_ECDSA_OK, ZG_SIGHASH_OK, ZG_ED_OK, ZG_GEN_BINDING, ZG_GEN_SPEND_AUTH, ZG_PREP_FIELD_BYTES, ZG_PREP_KIND_JOINSPLIT, ZG_PREP_KIND_JOINSPLIT_BN,
                  ZG_PREP_KIND_OUTPUT, ZG_PREP_KIND_SPEND};
 use super::{ZG_KIND_OUTPUT, ZG_KIND_SPEND, ZG_KIND_SPROUT, ZG_STATUS_OK};
@@ -96,6 +97,13 @@ pub struct EcdsaRequest {
     pub amount: u64,
 }
 
+/// the output an input spends: its script and its value
+#[derive(Clone)]
+pub struct Prevout {
+    pub script_pubkey: Vec<u8>,
+    pub amount: u64,
+}
+
 /// lookup(input_index, pubkey, sig, script_code, hashtype) -> the verdict of a request's check: answerable
 /// without the host computing a sighash
 pub type RequestLookup<'a> = dyn FnMut(usize, &[u8], &[u8], &[u8], u32) -> Result<bool, GpuError> + 'a;
@@ -145,6 +153,10 @@ pub struct Tx {
     pub branch_id: u32,
     pub ecdsa_requests: Vec<EcdsaRequest>,
     pub eval_rerun_requests: Option<EvalRerunRequests>,
+    /// the whole script check of template inputs on the GPU: one Prevout per input, set only
+    /// when script_class names every input of the transaction a template (P2PKH or P2PK). Needs raw; ecdsa_checks,
+    /// ecdsa_requests and both reruns must then be empty: no interpreter runs for this transaction
+    pub prevouts: Option<Vec<Prevout>>,
 }
 
 #[derive(Debug, Clone, PartialEq)]
@@ -175,6 +187,12 @@ pub trait Backend {
     /// (ZG_TX_* per transaction, hash per item, ZG_SIGHASH_* per item)
     fn sighash(&self, _txs: &[(Vec<u8>, u32)], _items: &[SighashItem]) -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
         Err(GpuError { code: -1, message: "this backend computes no signature hashes".to_string() })
+    }
+    /// verify_script of template inputs over (serialized transaction, branch id) under `flags` ->
+    /// (ZG_TX_* per transaction, ZG_INPUT_* per item, ZG_ECDSA_* detail per item, the hash checked per item)
+    fn inputs_verify(&self, _txs: &[(Vec<u8>, u32)], _items: &[InputItem], _flags: u32)
+                     -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<[u8; 32]>), GpuError> {
+        Err(GpuError { code: -1, message: "this backend verifies no template inputs".to_string() })
     }
     /// header statuses (ZG_HDR_*: the first failing of deserialize / Equihash / proof of work) for
     /// serialized 1487-byte headers against the compact `max_bits`
@@ -214,6 +232,10 @@ impl Backend for GpuVerifier {
     }
     fn sighash(&self, txs: &[(Vec<u8>, u32)], items: &[SighashItem]) -> Result<(Vec<u8>, Vec<[u8; 32]>, Vec<u8>), GpuError> {
         GpuVerifier::sighash(self, txs, items)
+    }
+    fn inputs_verify(&self, txs: &[(Vec<u8>, u32)], items: &[InputItem], flags: u32)
+                     -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<[u8; 32]>), GpuError> {
+        GpuVerifier::inputs_verify(self, txs, items, flags)
     }
     fn headers_verify(&self, headers: &[Vec<u8>], max_bits: u32) -> Result<Vec<u8>, GpuError> {
         Ok(GpuVerifier::headers_verify(self, headers, max_bits)?.into_iter().map(|r| r.0).collect())
@@ -574,6 +596,49 @@ fn eval_error<B: Backend>(v: &B, txs: &[Tx], idx: usize, table: &mut HashMap<Ecd
     (*rerun)(&mut lookup)
 }
 
+/// the eval errors of the transactions that carry prevouts, by window index: every input of theirs goes through ONE
+/// inputs_verify call; a transaction's error is Signature(lowest failing input, the interpreter's error). An input
+/// without a verdict (not a template, out of range, a transaction the GPU does not parse) is an Err: the caller's
+fn input_errors<B: Backend>(v: &B, txs: &[Tx], script_flags: u32) -> Result<HashMap<usize, Option<TxError>>, GpuError> {
+    let need: Vec<usize> = (0..txs.len()).filter(|&i| txs[i].prevouts.is_some()).collect();
+    let mut errors = HashMap::new();
+    for &i in &need {
+        let tx = &txs[i];
+        if tx.raw.is_none() {
+            return Err(GpuError { code: -1, message: format!("transaction {} carries prevouts but no raw bytes", i) });
+        }
+        if !tx.ecdsa_checks.is_empty() || !tx.ecdsa_requests.is_empty() || tx.eval_rerun.is_some() || tx.eval_rerun_requests.is_some() {
+            return Err(GpuError { code: -1, message: format!("transaction {} carries prevouts and ecdsa_checks, ecdsa_requests or a rerun", i) });
+        }
+        errors.insert(i, None);
+    }
+    if need.is_empty() {
+        return Ok(errors);
+    }
+    let raws: Vec<(Vec<u8>, u32)> = need.iter().map(|&i| (txs[i].raw.clone().unwrap(), txs[i].branch_id)).collect();
+    let mut items = Vec::new();
+    for (k, &i) in need.iter().enumerate() {
+        for (j, p) in txs[i].prevouts.as_ref().unwrap().iter().enumerate() {
+            items.push(InputItem { tx: k as u32, input_index: j as u32, script_pubkey: p.script_pubkey.clone(), amount: p.amount });
+        }
+    }
+    let (_, status, _, _) = v.inputs_verify(&raws, &items, script_flags)?;
+    for (it, st) in items.iter().zip(status) {
+        let i = need[it.tx as usize];
+        let name = match st {
+            ZG_INPUT_OK => continue,
+            ZG_INPUT_EQUALVERIFY => "EqualVerify",
+            ZG_INPUT_SIGNATURE_DER => "SignatureDer",
+            ZG_INPUT_EVAL_FALSE => "EvalFalse",
+            _ => return Err(GpuError { code: -1, message: format!("transaction {}: input {} was not verified (ZG_INPUT status {}); run its script on the host", i, it.input_index, st) }),
+        };
+        if errors[&i].is_none() {
+            errors.insert(i, Some(TxError::Signature(it.input_index as usize, name.to_string())));
+        }
+    }
+    Ok(errors)
+}
+
 fn tx_error(tx: &Tx, plan: &(Vec<Plan>, Vec<Plan>, Vec<Plan>), status: &[u8], pghr_status: &[u8], sp_ok: &[bool],
             bind_ok: bool, js_sig_ok: bool, eval: Option<TxError>) -> Option<TxError> {
     let (js, sp, out) = plan;
@@ -638,6 +703,13 @@ fn tx_error(tx: &Tx, plan: &(Vec<Plan>, Vec<Plan>, Vec<Plan>), status: &[u8], pg
 /// Ok(None) if every transaction passes, else Ok(Some((tx_index, error))) with the error the
 /// reference reports; Err only for a backend (GPU / runtime) failure.
 pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxError)>, GpuError> {
+    verify_block_flags(v, txs, ZG_SCRIPT_VERIFY_DERSIG)
+}
+
+/// verify_block with the script flags the window's template inputs (Tx::prevouts) are verified under (bip66_height
+/// is 0 on every network of network/src/consensus.rs: ZG_SCRIPT_VERIFY_DERSIG)
+pub fn verify_block_flags<B: Backend>(v: &B, txs: &[Tx], script_flags: u32) -> Result<Option<(usize, TxError)>, GpuError> {
+    let template = input_errors(v, txs, script_flags)?;
     // the sighashes the window leaves to the backend (Tx::raw), before the signature batches
     let resolved = resolve_sighashes(v, txs)?;
     let (owned, mut known) = match resolved {
@@ -656,7 +728,8 @@ pub fn verify_block<B: Backend>(v: &B, txs: &[Tx]) -> Result<Option<(usize, TxEr
     let mut table = ecdsa_table(v, txs)?;
     for (idx, (tx, plan)) in txs.iter().zip(&plans).enumerate() {
         // precedence: pre_error, then the eval error, then the JoinSplit and Sapling stages
-        let eval = if tx.pre_error.is_none() && !tx.ecdsa_checks.is_empty() { eval_error(v, txs, idx, &mut table, &mut known)? } else { None };
+        let eval = if let Some(e) = template.get(&idx) { e.clone() }
+                   else if tx.pre_error.is_none() && !tx.ecdsa_checks.is_empty() { eval_error(v, txs, idx, &mut table, &mut known)? } else { None };
         if let Some(e) = tx_error(tx, plan, &status, &pghr_status, &sp_ok[idx], bind_ok[idx], js_ok[idx], eval) {
             return Ok(Some((idx, e)));
         }

@@ -79,6 +79,20 @@ pub const ZG_SIGHASH_TX_MALFORMED: u8 = 1;
 pub const ZG_SIGHASH_TX_NONCANONICAL: u8 = 2;
 pub const ZG_SIGHASH_INPUT_RANGE: u8 = 3;
 pub const ZG_SIGHASH_NO_INPUT: u32 = 0xFFFF_FFFF;
+// zg_script_class / zg_inputs_verify: the template of a (script_sig, script_pubkey) pair, the one script flag a
+// template run reads, and an item's status (the interpreter's error, or why there is no verdict)
+pub const ZG_SCRIPT_HOST: u8 = 0;
+pub const ZG_SCRIPT_P2PKH: u8 = 1;
+pub const ZG_SCRIPT_P2PK: u8 = 2;
+pub const ZG_SCRIPT_VERIFY_DERSIG: u32 = 1;
+pub const ZG_INPUT_OK: u8 = 0;
+pub const ZG_INPUT_EQUALVERIFY: u8 = 1;
+pub const ZG_INPUT_SIGNATURE_DER: u8 = 2;
+pub const ZG_INPUT_EVAL_FALSE: u8 = 3;
+pub const ZG_INPUT_HOST: u8 = 4;
+pub const ZG_INPUT_TX_MALFORMED: u8 = 5;
+pub const ZG_INPUT_TX_NONCANONICAL: u8 = 6;
+pub const ZG_INPUT_RANGE: u8 = 7;
 // zg_blocks_verify: the first failing check of BlockVerifier::check (after the parser's two verdicts), and
 // the flags of every check that fails
 pub const ZG_BLK_OK: u8 = 0;
@@ -183,6 +197,12 @@ extern "C" {
                       n: usize, item_tx: *const u32, input_index: *const u32, scripts: *const u8,
                       script_off: *const u32, amount: *const u64, hashtype: *const u32, tx_status: *mut u8,
                       hashes: *mut u8, status: *mut u8) -> c_int;
+    pub fn zg_script_class(script_sig: *const u8, sig_len: usize, script_pubkey: *const u8, pk_len: usize,
+                           out: *mut u64) -> c_int;
+    pub fn zg_inputs_verify(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64, tx_branch_id: *const u32,
+                            n: usize, item_tx: *const u32, input_index: *const u32, prev_scripts: *const u8,
+                            prev_off: *const u32, amount: *const u64, flags: u32, tx_status: *mut u8,
+                            status: *mut u8, detail: *mut u8, hashes: *mut u8) -> c_int;
     pub fn zg_block_layout(block: *const u8, len: usize, out: *mut u64, tx_off: *mut u64, tx_off_cap: usize) -> c_int;
     pub fn zg_txids(ctx: *mut ZgCtx, n: usize, arena: *const u8, off: *const u64, hashes: *mut u8) -> c_int;
     pub fn zg_blocks_verify(ctx: *mut ZgCtx, nblk: usize, blocks: *const u8, blk_off: *const u64,

@@ -57,6 +57,28 @@ pub fn tx_layout(raw: &[u8]) -> (u8, [u64; 8]) {
     (rc as u8, out)
 }
 
+/// One template input to verify (GpuVerifier::inputs_verify): input `input_index` of transaction number `tx` of the
+/// call, spending an output of value `amount` whose script is `script_pubkey`.
+#[derive(Clone, Debug, PartialEq, Eq, Hash)]
+pub struct InputItem {
+    pub tx: u32,
+    pub input_index: u32,
+    pub script_pubkey: Vec<u8>,
+    pub amount: u64,
+}
+
+/// zg_script_class: the template matcher zg_inputs_verify runs -> [class (ffi::ZG_SCRIPT_*), offset and length of the
+/// signature push in script_sig, offset and length of the key push (P2PKH: in script_sig, P2PK: in script_pubkey)];
+/// all zero for ZG_SCRIPT_HOST. CPU, no context.
+pub fn script_class(script_sig: &[u8], script_pubkey: &[u8]) -> [u64; 5] {
+    let mut out = [0u64; 5];
+    let pad = [0u8; 1];
+    let s = if script_sig.is_empty() { pad.as_ptr() } else { script_sig.as_ptr() };
+    let p = if script_pubkey.is_empty() { pad.as_ptr() } else { script_pubkey.as_ptr() };
+    unsafe { ffi::zg_script_class(s, script_sig.len(), p, script_pubkey.len(), out.as_mut_ptr()) };
+    out
+}
+
 /// One batch slot on one GPU (device buffers only; the streams and the prepared verifying keys
 /// are shared per device inside libzg). Several slots keep several windows in flight.
 pub struct GpuVerifier {
@@ -292,6 +314,55 @@ impl GpuVerifier {
         status.truncate(n);
         let hs = (0..n).map(|i| { let mut h = [0u8; 32]; h.copy_from_slice(&hashes[32 * i..32 * i + 32]); h }).collect();
         Ok((tx_status, hs, status))
+    }
+
+    /// verify_script (script/src/interpreter.rs:288-360) of pay-to-pubkey-hash and pay-to-pubkey inputs over the
+    /// serialized transactions `txs` (raw bytes, consensus branch id), under `flags` (ffi::ZG_SCRIPT_VERIFY_DERSIG
+    /// or 0) -> (ZG_TX_* per transaction, ZG_INPUT_* per item, the ZG_ECDSA_* detail of an EVAL_FALSE item, the
+    /// signature hash that was checked or zero). ZG_INPUT_HOST: not a template, the caller runs verify_script.
+    pub fn inputs_verify(&self, txs: &[(Vec<u8>, u32)], items: &[InputItem], flags: u32)
+                         -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<[u8; 32]>), GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let (ntx, n) = (txs.len(), items.len());
+        let mut arena = Vec::new();
+        let mut tx_off = Vec::with_capacity(ntx + 1);
+        let mut branch = Vec::with_capacity(ntx + 1);
+        for (raw, b) in txs.iter() {
+            tx_off.push(arena.len() as u64);
+            arena.extend_from_slice(raw);
+            branch.push(*b);
+        }
+        tx_off.push(arena.len() as u64);
+        arena.push(0);
+        branch.push(0);
+        let mut prev = Vec::new();
+        let mut prev_off = Vec::with_capacity(n + 1);
+        for it in items.iter() {
+            prev_off.push(prev.len() as u32);
+            prev.extend_from_slice(&it.script_pubkey);
+        }
+        if prev.len() > u32::max_value() as usize {
+            return Err(GpuError { code: -1, message: "inputs_verify: the previous scripts exceed 4 GiB".to_string() });
+        }
+        prev_off.push(prev.len() as u32);
+        prev.push(0);
+        let item_tx: Vec<u32> = items.iter().map(|it| it.tx).chain(Some(0)).collect();
+        let index: Vec<u32> = items.iter().map(|it| it.input_index).chain(Some(0)).collect();
+        let amount: Vec<u64> = items.iter().map(|it| it.amount).chain(Some(0)).collect();
+        let mut tx_status = vec![0u8; ntx + 1];
+        let mut status = vec![0u8; n + 1];
+        let mut detail = vec![0u8; n + 1];
+        let mut hashes = vec![0u8; 32 * n + 1];
+        check(self.ctx, unsafe {
+            ffi::zg_inputs_verify(self.ctx, ntx, arena.as_ptr(), tx_off.as_ptr(), branch.as_ptr(), n, item_tx.as_ptr(),
+                                  index.as_ptr(), prev.as_ptr(), prev_off.as_ptr(), amount.as_ptr(), flags,
+                                  tx_status.as_mut_ptr(), status.as_mut_ptr(), detail.as_mut_ptr(), hashes.as_mut_ptr())
+        })?;
+        tx_status.truncate(ntx);
+        status.truncate(n);
+        detail.truncate(n);
+        let hs = (0..n).map(|i| { let mut h = [0u8; 32]; h.copy_from_slice(&hashes[32 * i..32 * i + 32]); h }).collect();
+        Ok((tx_status, status, detail, hs))
     }
 
     /// verify_equihash_solution (equihash.rs:80-172) for the instance `params` (ffi::ZG_EQ_*): per item

@@ -30,7 +30,11 @@ its script run repeated with the real verdicts (Tx.eval_rerun). The signature ha
 the GPU as well: a transaction that carries its serialized bytes (Tx.raw, Tx.branch_id) and
 no sighash gets the no-input hash the acceptor computes (accept_transaction.rs:374-386), and its checks may be
 handed in without their hash (Tx.ecdsa_requests: script code, hashtype and amount instead); all of the window's
-are computed in ONE zg_sighash call before the signature batches. The collector prepares every public input of
+are computed in ONE zg_sighash call before the signature batches. A transaction whose inputs are all pay-to-pubkey-hash
+or pay-to-pubkey spends (zg.script_class says so before any interpreter runs) needs no script run at all (SURVEY.md
+8(f) f15): it carries the outputs it spends (Tx.prevouts) instead of checks, and every such input of the window is
+verified -- HASH160, the encoding check, the signature hash and the signature -- in ONE zg_inputs_verify call. The
+collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
 verifies all Groth16 proofs of the window in
@@ -110,6 +114,14 @@ class EcdsaRequest:
 
 
 @dataclass
+class Prevout:
+    """the output an input spends: its script and its value (the `previous_output` the acceptor looks up,
+    accept_transaction.rs:363-422)"""
+    script_pubkey: bytes
+    amount: int
+
+
+@dataclass
 class Tx:
     """the shielded-proof view of one transaction, with the caller's non-Groth16 outcomes"""
     pre_error: Optional[str] = None           # first failing check before the JoinSplit stage
@@ -144,6 +156,10 @@ class Tx:
     raw: Optional[bytes] = None
     branch_id: Optional[int] = None
     ecdsa_requests: List[EcdsaRequest] = field(default_factory=list)
+    # the whole script check of template inputs on the GPU: one Prevout per input, set only when
+    # zg.script_class names every input of the transaction a template (P2PKH or P2PK). Needs raw and branch_id;
+    # ecdsa_checks, ecdsa_requests and eval_rerun must then be empty: no interpreter runs for this transaction
+    prevouts: Optional[List[Prevout]] = None
 
 
 _POOL = None
@@ -451,9 +467,43 @@ def _eval_errors(txs, ctx, verify_ecdsa, resolve=None):
     return eval_error
 
 
-def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None, eval_error=None):
+def _input_errors(txs, ctx, inputs_verify, script_flags):
+    """-> {window index: eval error or None} of the transactions that carry prevouts. Every input of theirs goes
+    through ONE inputs_verify(raws, branch_ids, items, flags) call (default ctx.inputs_verify); a transaction's
+    error is ("Signature", index, name) of its lowest failing input (TransactionEval::check walks the inputs in
+    order, accept_transaction.rs:363-422), name the interpreter's error. An input that comes back without a
+    verdict (not a template, out of range, a transaction the GPU does not parse) raises: it is the caller's."""
+    need = [i for i, tx in enumerate(txs) if tx.prevouts is not None]
+    for i in need:
+        tx = txs[i]
+        if tx.raw is None or tx.branch_id is None:
+            raise ValueError("transaction %d carries prevouts but no raw bytes or no branch id" % i)
+        if tx.ecdsa_checks or tx.ecdsa_requests or tx.eval_rerun is not None:
+            raise ValueError("transaction %d carries prevouts and ecdsa_checks, ecdsa_requests or eval_rerun: "
+                             "a transaction of template inputs has no interpreter run" % i)
+    if not need:
+        return {}
+    if inputs_verify is None:
+        if ctx is None:
+            raise zg.ZgError(-1, "transactions carry prevouts but no backend was given (pass ctx= or inputs_verify=)")
+        inputs_verify = ctx.inputs_verify
+    items = [(k, j, bytes(p.script_pubkey), p.amount) for k, i in enumerate(need) for j, p in enumerate(txs[i].prevouts)]
+    res = inputs_verify([bytes(txs[i].raw) for i in need], [txs[i].branch_id for i in need], items, script_flags)
+    errors = {i: None for i in need}
+    for (k, j, _, _), st in zip(items, res[1]):
+        i = need[k]
+        if st not in (zg.INPUT_OK,) + tuple(zg.INPUT_ERRORS):
+            raise zg.ZgError(-1, "transaction %d: input %d was not verified (ZG_INPUT status %d); run its script on "
+                                 "the host" % (i, j, st))
+        if st != zg.INPUT_OK and errors[i] is None:
+            errors[i] = ("Signature", j, zg.INPUT_ERRORS[st])
+    return errors
+
+
+def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None, eval_error=None,
+              input_error=None):
     """the reference's first error of one transaction, given the proof statuses; eval_error(tx) is asked
-    only when no earlier check failed"""
+    only when no earlier check failed. input_error: the eval error of a transaction of template inputs"""
     if js_sig_ok is None:
         js_sig_ok = tx.js_sig_ok
     js_plan, sp_plan, out_plan = plan
@@ -463,6 +513,8 @@ def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig
         bind_ok = tx.binding_ok
     if tx.pre_error:
         return tx.pre_error
+    if input_error is not None:
+        return input_error
     if eval_error is not None and tx.ecdsa_checks:
         err = eval_error(tx)
         if err is not None:
@@ -511,7 +563,8 @@ def _chunked(verify, cap):
 
 
 def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
-                 verify_js_sigs=None, verify_ecdsa=None, sighash=None):
+                 verify_js_sigs=None, verify_ecdsa=None, sighash=None, inputs_verify=None,
+                 script_flags=zg.SCRIPT_VERIFY_DERSIG):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -533,7 +586,12 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     serialized bytes (Tx.raw, Tx.branch_id) get the sighashes they lack -- the no-input one, and one per
     Tx.ecdsa_requests entry -- from sighash(raws, branch_ids, items) -> (tx statuses, hashes, statuses),
     default ctx.sighash (ONE zg_sighash call for the window, before the signature batches); a transaction
-    the GPU reports as malformed or non-canonical raises ZgError and is the caller's to hash."""
+    the GPU reports as malformed or non-canonical raises ZgError and is the caller's to hash. Transactions whose
+    inputs are all templates (Tx.prevouts) have every input verified through inputs_verify(raws, branch_ids, items,
+    flags) -> (tx statuses, statuses, ...), default ctx.inputs_verify (ONE zg_inputs_verify call for the window, made
+    with script_flags: bip66_height is 0 on every network); their eval error stands where eval_rerun's does, and an
+    input the GPU gives no verdict on raises ZgError."""
+    input_errors = _input_errors(txs, ctx, inputs_verify, script_flags)
     txs, resolve = _resolve_sighashes(txs, ctx, sighash)
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:
@@ -561,7 +619,8 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     js_ok = _js_sig_verdicts(txs, ctx, verify_js_sigs)
     eval_error = _eval_errors(txs, ctx, verify_ecdsa, resolve)
     for idx, (tx, plan) in enumerate(zip(txs, plans)):
-        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx], eval_error)
+        err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx], eval_error,
+                        input_errors.get(idx))
         if err is not None:
             return idx, err
     return None

@@ -1,14 +1,16 @@
-// zg_calls.hip -- the one-shot entries of the C ABI (include/zg.h): signatures, signature hashes, block
+// zg_calls.hip -- the one-shot entries of the C ABI (include/zg.h): signatures, signature hashes, template inputs, block
 // bodies and headers, input preparation, note-commitment trees and PGHR13 proofs. Each validates its
 // arguments, takes the context's lock and device, moves its buffers (zg_host.h) and calls the launch_*,
 // merkle_* or bn_* of the unit that holds the kernels; none is launched from here. The Groth16 batch
 // pipeline and the context's lifecycle are zg.hip.
 #include <array>
+#include <type_traits>
 
 #include "zg_host.h"
 #include "zg_blocks.h"
 #include "zg_ecdsa.h"    // ZG_EC_COMB_*
 #include "zg_ed25519.h"  // ZG_ED_COMB_*
+#include "zg_inputs.h"
 #include "zg_jubjub.h"   // ZG_JJ_COMB_*
 #include "zg_prep.h"
 #include "zg_sighash.h"
@@ -32,6 +34,9 @@ hipError_t launch_sighash_digests(hipStream_t st, const uint8_t* arena, const Sh
 hipError_t launch_sighash_items(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const uint32_t* in_off,
                                 const uint32_t* out_off, const uint8_t* digests, const uint8_t* scripts,
                                 const ShDevItem* items, int n, uint8_t* hashes);
+hipError_t launch_script_items(hipStream_t st, const uint8_t* arena, const uint8_t* prev, const ScDevItem* items, int n,
+                               uint32_t flags, uint8_t* pubkeys, uint8_t* pubkey_len, uint8_t* sigs,
+                               uint8_t* status);                                                   // zg_script.hip
 hipError_t launch_txid(hipStream_t st, const uint8_t* arena, const TxidSlice* slices, int n, uint8_t* out);  // zg_blocks.hip
 hipError_t launch_block_merkle(hipStream_t st, const uint8_t* arena, const MerkleBlk* blks, int nblk,
                                const uint8_t* ids, uint8_t* ping, uint8_t* pong, uint8_t* roots, uint8_t* match);
@@ -171,6 +176,113 @@ extern "C" int zg_ecdsa_verify(zg_ctx* ctx, size_t n, const uint8_t* pubkeys, co
 }
 
 // ------------------------------------------------------------------ signature hashes (zg_sighash.h)
+// The planning half of a signature-hash launch, shared by zg_sighash and zg_inputs_verify: the layouts
+// (sh_plan_txs), the items a lane takes as the caller gathers them (sh_plan_add), then the launch order and the
+// digest jobs (sh_plan_finish)
+struct ShPlan {
+  std::vector<ShDevTx> dtx;
+  std::vector<uint32_t> in_off, out_off;
+  std::vector<ShDevItem> items;  // as gathered; sh_plan_finish orders them by cost, the dearest first
+  std::vector<uint64_t> cost;    // per gathered item
+  std::vector<uint8_t> need;     // per transaction: the digests its items read
+  std::vector<uint32_t> jobs;    // (transaction << 3) | digest
+  uint32_t ndig = 0;
+};
+// the layouts: every offset a lane follows is checked here
+static void sh_plan_txs(ShPlan& P, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
+                        uint8_t* tx_status) {
+  const uint64_t base0 = ntx ? tx_off[0] : 0;
+  P.dtx.assign(ntx ? ntx : 1, ShDevTx{});
+  for (size_t t = 0; t < ntx; t++) {
+    ShDevTx& d = P.dtx[t];
+    tx_status[t] = (uint8_t)tx_parse(txs + tx_off[t], (size_t)(tx_off[t + 1] - tx_off[t]), d.L, P.in_off, P.out_off);
+    d.base = (uint32_t)(tx_off[t] - base0);
+    d.branch_id = tx_branch_id[t];
+    d.dig = 0;
+  }
+  P.need.assign(ntx ? ntx : 1, 0);
+}
+// an item of a transaction that parsed, its index in range where the format asks for that
+static void sh_plan_add(ShPlan& P, const ShDevItem& it) {
+  const TxLayout& L = P.dtx[it.tx].L;
+  const uint32_t base = sh_base(it.hashtype), acp = it.hashtype & 0x80;
+  const uint32_t slen = it.script_len;
+  P.items.push_back(it);
+  if (L.sigver) {
+    P.need[it.tx] |= (uint8_t)((acp ? 0 : 1 << SH_PREVOUTS) | (!acp && base == SH_ALL ? 1 << SH_SEQUENCES : 0) |
+                               (base == SH_ALL ? 1 << SH_OUTPUTS : 0) | (L.n_js ? 1 << SH_JOINSPLITS : 0) |
+                               (L.sigver == 2 && L.n_spend ? 1 << SH_SPENDS : 0) |
+                               (L.sigver == 2 && L.n_sout ? 1 << SH_SOUTPUTS : 0));
+    P.cost.push_back(2 * (uint64_t)(512 + slen));  // a BLAKE2b compression per 128 bytes, about two SHA-256 ones
+  } else {
+    P.cost.push_back(acp ? 256 + (uint64_t)slen + L.consumed - L.lock_off : (uint64_t)L.consumed + slen);
+  }
+}
+static void sh_plan_finish(ShPlan& P, size_t ntx) {
+  const std::vector<uint64_t>& cost = P.cost;
+  const std::vector<uint8_t>& need = P.need;
+  std::vector<uint32_t> order(P.items.size());
+  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
+  std::vector<ShDevItem> sorted(P.items.size());
+  for (size_t k = 0; k < order.size(); k++) sorted[k] = P.items[order[k]];
+  P.items.swap(sorted);
+  for (size_t t = 0; t < ntx; t++)
+    if (need[t]) {
+      P.dtx[t].dig = P.ndig++;
+      for (int w = 0; w < SH_DIGESTS; w++)
+        if (need[t] >> w & 1) P.jobs.push_back((uint32_t)(t << 3) | (uint32_t)w);
+    }
+}
+// what the two kernels read and write, on the device
+struct ShDev {
+  uint8_t *arena, *scripts, *dig, *hash;  // hash: 32 bytes per planned item, in the plan's order
+  ShDevTx* txs;
+  ShDevItem* items;
+  uint32_t *in, *out, *jobs;
+};
+// the buffers' sizes, in the order sh_upload asks its owner for them
+static std::array<size_t, 9> sh_dev_bytes(const ShPlan& P, size_t ntx, size_t arena_bytes, size_t script_bytes) {
+  const size_t m = P.items.size();
+  return {arena_bytes + 8,  // (most of these are longer than what is copied into them)
+          script_bytes + 8, (size_t)32 * SH_DIGESTS * (P.ndig ? P.ndig : 1), 32 * m, sizeof(ShDevTx) * ntx,
+          sizeof(ShDevItem) * m, sizeof(uint32_t) * (P.in_off.size() + 1), sizeof(uint32_t) * (P.out_off.size() + 1),
+          sizeof(uint32_t) * (P.jobs.size() + 1)};
+}
+// alloc(&pointer, bytes) -> hipError_t: the call's own allocations (zg_sighash) or parts of a context's arena
+template <class Alloc>
+static int sh_upload(zg_ctx* ctx, Alloc alloc, const ShPlan& P, size_t ntx, const uint8_t* arena, size_t arena_bytes,
+                     const uint8_t* scripts, size_t script_bytes, ShDev& D) {
+  const size_t m = P.items.size();
+  const std::array<size_t, 9> b = sh_dev_bytes(P, ntx, arena_bytes, script_bytes);
+  HIPCHK(alloc(&D.arena, b[0]));
+  HIPCHK(alloc(&D.scripts, b[1]));
+  HIPCHK(alloc(&D.dig, b[2]));
+  HIPCHK(alloc(&D.hash, b[3]));
+  HIPCHK(alloc(&D.txs, b[4]));
+  HIPCHK(alloc(&D.items, b[5]));
+  HIPCHK(alloc(&D.in, b[6]));
+  HIPCHK(alloc(&D.out, b[7]));
+  HIPCHK(alloc(&D.jobs, b[8]));
+  HIPCHK(hipMemcpyAsync(D.arena, arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (script_bytes) HIPCHK(hipMemcpyAsync(D.scripts, scripts, script_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(D.txs, P.dtx.data(), sizeof(ShDevTx) * ntx, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(D.items, P.items.data(), sizeof(ShDevItem) * m, hipMemcpyHostToDevice, ctx->stream));
+  if (!P.in_off.empty())
+    HIPCHK(hipMemcpyAsync(D.in, P.in_off.data(), sizeof(uint32_t) * P.in_off.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!P.out_off.empty())
+    HIPCHK(hipMemcpyAsync(D.out, P.out_off.data(), sizeof(uint32_t) * P.out_off.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!P.jobs.empty())
+    HIPCHK(hipMemcpyAsync(D.jobs, P.jobs.data(), sizeof(uint32_t) * P.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+  return ZG_OK;
+}
+static hipError_t sh_launch(zg_ctx* ctx, const ShPlan& P, const ShDev& D) {
+  const hipError_t e = launch_sighash_digests(ctx->stream, D.arena, D.txs, D.in, D.out, D.jobs, (int)P.jobs.size(), D.dig);
+  if (e != hipSuccess) return e;
+  return launch_sighash_items(ctx->stream, D.arena, D.txs, D.in, D.out, D.dig, D.scripts, D.items, (int)P.items.size(),
+                              D.hash);
+}
+
 extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
                           const uint32_t* tx_branch_id, size_t n, const uint32_t* item_tx, const uint32_t* input_index,
                           const uint8_t* scripts, const uint32_t* script_off, const uint64_t* amount,
@@ -185,25 +297,12 @@ extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uin
   std::lock_guard<std::mutex> g(ctx->mu);
   if (!ntx && !n) return ZG_OK;
 
-  // the layouts: every offset a lane follows is checked here
-  const uint64_t base0 = ntx ? tx_off[0] : 0;
-  std::vector<ShDevTx> dtx(ntx ? ntx : 1);
-  std::vector<uint32_t> in_off, out_off;
-  for (size_t t = 0; t < ntx; t++) {
-    ShDevTx& d = dtx[t];
-    tx_status[t] = (uint8_t)tx_parse(txs + tx_off[t], (size_t)(tx_off[t + 1] - tx_off[t]), d.L, in_off, out_off);
-    d.base = (uint32_t)(tx_off[t] - base0);
-    d.branch_id = tx_branch_id[t];
-    d.dig = 0;
-  }
-  // the items a lane takes, and the digests they read
-  std::vector<ShDevItem> items;
-  std::vector<uint64_t> cost;
-  std::vector<uint8_t> need(ntx ? ntx : 1, 0);
-  items.reserve(n);
+  ShPlan P;
+  sh_plan_txs(P, ntx, txs, tx_off, tx_branch_id, tx_status);
+  // the items a lane takes
+  P.items.reserve(n);
   for (size_t i = 0; i < n; i++) {
-    const ShDevTx& d = dtx[item_tx[i]];
-    const TxLayout& L = d.L;
+    const TxLayout& L = P.dtx[item_tx[i]].L;
     const uint8_t ts = tx_status[item_tx[i]];
     memset(hashes + 32 * i, 0, 32);
     status[i] = ts == ZG_TX_MALFORMED ? ZG_SIGHASH_TX_MALFORMED : ts == ZG_TX_NONCANONICAL ? ZG_SIGHASH_TX_NONCANONICAL
@@ -211,72 +310,157 @@ extern "C" int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uin
                                                                                              : ZG_SIGHASH_OK;
     if (status[i] != ZG_SIGHASH_OK) continue;
     const uint32_t base = sh_base(hashtype[i]), acp = hashtype[i] & 0x80;
-    const uint32_t slen = script_off[i + 1] - script_off[i];
     if (!L.sigver && input_index[i] >= L.n_in && (acp || base == SH_SINGLE)) continue;  // the zero hash, OK
-    items.push_back(ShDevItem{item_tx[i], input_index[i], script_off[i] - script_off[0], slen, hashtype[i], (uint32_t)i,
-                              amount[i]});
-    if (L.sigver) {
-      need[item_tx[i]] |= (uint8_t)((acp ? 0 : 1 << SH_PREVOUTS) | (!acp && base == SH_ALL ? 1 << SH_SEQUENCES : 0) |
-                                    (base == SH_ALL ? 1 << SH_OUTPUTS : 0) | (L.n_js ? 1 << SH_JOINSPLITS : 0) |
-                                    (L.sigver == 2 && L.n_spend ? 1 << SH_SPENDS : 0) |
-                                    (L.sigver == 2 && L.n_sout ? 1 << SH_SOUTPUTS : 0));
-      cost.push_back(2 * (uint64_t)(512 + slen));  // a BLAKE2b compression per 128 bytes, about two SHA-256 ones
-    } else {
-      cost.push_back(acp ? 256 + (uint64_t)slen + L.consumed - L.lock_off : (uint64_t)L.consumed + slen);
-    }
+    sh_plan_add(P, ShDevItem{item_tx[i], input_index[i], script_off[i] - script_off[0],
+                             script_off[i + 1] - script_off[i], hashtype[i], (uint32_t)i, amount[i]});
   }
-  std::vector<uint32_t> order(items.size());
-  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-  std::vector<ShDevItem> sorted(items.size() ? items.size() : 1);
-  for (size_t k = 0; k < order.size(); k++) sorted[k] = items[order[k]];
-  std::vector<uint32_t> jobs;
-  uint32_t ndig = 0;
-  for (size_t t = 0; t < ntx; t++)
-    if (need[t]) {
-      dtx[t].dig = ndig++;
-      for (int w = 0; w < SH_DIGESTS; w++)
-        if (need[t] >> w & 1) jobs.push_back((uint32_t)(t << 3) | (uint32_t)w);
-    }
-  const size_t m = items.size();
+  sh_plan_finish(P, ntx);
+  const size_t m = P.items.size();
   if (!m) return ZG_OK;
 
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0), script_bytes = (size_t)script_off[n] - script_off[0];
+  const uint64_t base0 = tx_off[0];
   DevScratch s;
-  uint8_t *darena, *dscripts, *ddig, *dhash;
-  ShDevTx* dtxs;
-  ShDevItem* ditems;
-  uint32_t *din, *dout, *djobs;
-  HIPCHK(s.alloc(&darena, arena_bytes + 8));  // (most of these are longer than what is copied into them)
-  HIPCHK(s.alloc(&dscripts, script_bytes + 8));
-  HIPCHK(s.alloc(&ddig, (size_t)32 * SH_DIGESTS * (ndig ? ndig : 1)));
-  HIPCHK(s.alloc(&dhash, 32 * m));
-  HIPCHK(s.alloc(&dtxs, sizeof(ShDevTx) * ntx));
-  HIPCHK(s.alloc(&ditems, sizeof(ShDevItem) * m));
-  HIPCHK(s.alloc(&din, sizeof(uint32_t) * (in_off.size() + 1)));
-  HIPCHK(s.alloc(&dout, sizeof(uint32_t) * (out_off.size() + 1)));
-  HIPCHK(s.alloc(&djobs, sizeof(uint32_t) * (jobs.size() + 1)));
-  HIPCHK(hipMemcpyAsync(darena, txs + base0, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (script_bytes)
-    HIPCHK(hipMemcpyAsync(dscripts, scripts + script_off[0], script_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dtxs, dtx.data(), sizeof(ShDevTx) * ntx, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ditems, sorted.data(), sizeof(ShDevItem) * m, hipMemcpyHostToDevice, ctx->stream));
-  if (!in_off.empty())
-    HIPCHK(hipMemcpyAsync(din, in_off.data(), sizeof(uint32_t) * in_off.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (!out_off.empty())
-    HIPCHK(hipMemcpyAsync(dout, out_off.data(), sizeof(uint32_t) * out_off.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (!jobs.empty())
-    HIPCHK(hipMemcpyAsync(djobs, jobs.data(), sizeof(uint32_t) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(sig_timed(ctx, [&] {
-    const hipError_t e = launch_sighash_digests(ctx->stream, darena, dtxs, din, dout, djobs, (int)jobs.size(), ddig);
-    if (e != hipSuccess) return e;
-    return launch_sighash_items(ctx->stream, darena, dtxs, din, dout, ddig, dscripts, ditems, (int)m, dhash);
-  }));
+  ShDev D;
+  const int rc = sh_upload(ctx, [&](auto** p, size_t bytes) { return s.alloc(p, bytes); }, P, ntx, txs + base0,
+                           (size_t)(tx_off[ntx] - base0), scripts + script_off[0],
+                           (size_t)script_off[n] - script_off[0], D);
+  if (rc) return rc;
+  HIPCHK(sig_timed(ctx, [&] { return sh_launch(ctx, P, D); }));
   std::vector<uint8_t> hh(32 * m);
-  HIPCHK(hipMemcpyAsync(hh.data(), dhash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(sig_sync(ctx));
-  for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * sorted[k].slot, hh.data() + 32 * k, 32);
+  for (size_t k = 0; k < m; k++) memcpy(hashes + (size_t)32 * P.items[k].slot, hh.data() + 32 * k, 32);
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ template inputs (zg_script.h, zg_inputs.h)
+// where input k's script_sig lies in a parsed, canonical transaction: after the outpoint and the compact size
+static void input_script_sig(const uint8_t* tx, const uint32_t* in_off, uint32_t k, uint32_t* off, uint32_t* len) {
+  const uint32_t o = in_off[k] + 36, tag = tx[o];
+  const uint32_t w = tag < 0xfd ? 1 : tag == 0xfd ? 3 : tag == 0xfe ? 5 : 9;
+  *off = o + w;
+  *len = in_off[k + 1] - 4 - *off;
+}
+
+extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                                const uint32_t* tx_branch_id, size_t n, const uint32_t* item_tx,
+                                const uint32_t* input_index, const uint8_t* prev_scripts, const uint32_t* prev_off,
+                                const uint64_t* amount, uint32_t flags, uint8_t* tx_status, uint8_t* status,
+                                uint8_t* detail, uint8_t* hashes) {
+  if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status)) ||
+      (n && (!item_tx || !input_index || !prev_scripts || !prev_off || !amount || !status)) || ntx > (1u << 30) ||
+      n > (1u << 30) || (flags & ~(uint32_t)ZG_SCRIPT_VERIFY_DERSIG))
+    return ZG_E_INVAL;
+  if (!offsets_ok(tx_off, ntx, 1ull << 31) || !offsets_ok(prev_off, n, 0)) return ZG_E_INVAL;
+  for (size_t i = 0; i < n; i++)
+    if (item_tx[i] >= ntx) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (!ntx && !n) return ZG_OK;
+
+  ShPlan P;
+  sh_plan_txs(P, ntx, txs, tx_off, tx_branch_id, tx_status);
+  // the template inputs: the matcher validates every offset a lane of k_script_items follows
+  const uint32_t prev0 = n ? prev_off[0] : 0;
+  std::vector<ScDevItem> rec(n ? n : 1);
+  P.items.reserve(n);
+  for (size_t i = 0; i < n; i++) {
+    const ShDevTx& d = P.dtx[item_tx[i]];
+    const uint8_t ts = tx_status[item_tx[i]];
+    if (detail) detail[i] = 0;
+    if (hashes) memset(hashes + 32 * i, 0, 32);
+    status[i] = ts == ZG_TX_MALFORMED ? ZG_INPUT_TX_MALFORMED : ts == ZG_TX_NONCANONICAL ? ZG_INPUT_TX_NONCANONICAL
+              : input_index[i] >= d.L.n_in ? ZG_INPUT_RANGE : ZG_INPUT_HOST;
+    if (status[i] != ZG_INPUT_HOST) continue;
+    const uint8_t* tx = txs + tx_off[item_tx[i]];
+    uint32_t so, sl;
+    input_script_sig(tx, P.in_off.data() + d.L.in_idx, input_index[i], &so, &sl);
+    const uint8_t* pk = prev_scripts + prev_off[i];
+    const uint32_t pl = prev_off[i + 1] - prev_off[i];
+    const ScriptClass c = script_class(tx + so, sl, pk, pl);
+    if (c.cls == SCRIPT_HOST) continue;
+    status[i] = ZG_INPUT_OK;
+    const uint32_t poff = prev_off[i] - prev0;
+    ScDevItem& r = rec[i];
+    r.cls = c.cls;
+    r.sig_off = d.base + so + c.sig_off, r.sig_len = c.sig_len;
+    r.key_off = c.cls == SCRIPT_P2PKH ? d.base + so + c.key_off : poff + c.key_off, r.key_len = c.key_len;
+    r.h160_off = poff + 3;
+    r.der_off = 0, r.pad = 0;
+    // the hashtype: the signature's last byte (check_signature, interpreter.rs:27); none for an empty push,
+    // whose hash no verdict reads
+    const uint32_t hashtype = c.sig_len ? tx[so + c.sig_off + c.sig_len - 1] : 1;
+    sh_plan_add(P, ShDevItem{item_tx[i], input_index[i], poff, pl, hashtype, (uint32_t)i, amount[i]});
+  }
+  sh_plan_finish(P, ntx);
+  const size_t m = P.items.size();
+  if (!m) return ZG_OK;  // HOST, range and transaction errors only: nothing is launched
+
+  std::vector<ScDevItem> srec(m);
+  std::vector<uint32_t> sig_off(m + 1);
+  uint64_t der_bytes = 0;  // (items may name one input many times: the sum is not bounded by the arena's size)
+  for (size_t k = 0; k < m; k++) {
+    srec[k] = rec[P.items[k].slot];
+    srec[k].der_off = sig_off[k] = (uint32_t)der_bytes;
+    der_bytes += srec[k].sig_len ? srec[k].sig_len - 1 : 0;
+    if (der_bytes > 0xffffffffull) return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: the signatures exceed 4 GiB");
+  }
+  sig_off[m] = (uint32_t)der_bytes;
+
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint32_t* comb = nullptr;
+  int rc = comb_table(ctx, &ctx->dev->ec_comb, sizeof(uint32_t) * ZG_EC_COMB_WORDS * ZG_EC_COMB_POINTS, launch_ec_comb,
+                      "secp256k1 comb table", &comb);
+  if (rc) return rc;
+  // the context's arena (allocating per call costs more wall time than the kernels), every part 256-aligned
+  const uint64_t base0 = tx_off[0];
+  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0), prev_bytes = (size_t)prev_off[n] - prev0;
+  const size_t own[7] = {sizeof(ScDevItem) * m, sizeof(uint32_t) * (m + 1), (size_t)ZG_ECDSA_PUBKEY_STRIDE * m, m,
+                         (size_t)der_bytes + 1, m, m};
+  size_t need = 0;
+  for (size_t b : sh_dev_bytes(P, ntx, arena_bytes, prev_bytes)) need += Carve::span(b, 256);
+  for (size_t b : own) need += Carve::span(b, 256);
+  DevArena& A = ctx->inputs_arena;
+  HIPCHK(A.reserve(need, ctx->stream));
+  ShDev D;
+  rc = sh_upload(ctx, [&](auto** p, size_t bytes) {
+    using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
+    *p = (T*)A.carve<uint8_t>(bytes, 256);  // (no part is empty: sh_dev_bytes)
+    return hipSuccess;
+  }, P, ntx, txs + base0, arena_bytes, prev_scripts + prev0, prev_bytes, D);
+  if (rc) return rc;
+  ScDevItem* const drec = (ScDevItem*)A.carve<uint8_t>(own[0], 256);
+  uint32_t* const doff = (uint32_t*)A.carve<uint8_t>(own[1], 256);
+  uint8_t* const dpk = A.carve<uint8_t>(own[2], 256);
+  uint8_t* const dlen = A.carve<uint8_t>(own[3], 256);
+  uint8_t* const dsig = A.carve<uint8_t>(own[4], 256);
+  uint8_t* const dsc = A.carve<uint8_t>(own[5], 256);
+  uint8_t* const dec = A.carve<uint8_t>(own[6], 256);
+  HIPCHK(hipMemcpyAsync(drec, srec.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(doff, sig_off.data(), own[1], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] {
+    hipError_t e = launch_script_items(ctx->stream, D.arena, D.scripts, drec, (int)m, flags, dpk, dlen, dsig, dsc);
+    if (e == hipSuccess) e = sh_launch(ctx, P, D);
+    if (e == hipSuccess) e = launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, D.hash, (int)m, comb, dec);
+    return e;
+  }));
+  std::vector<uint8_t> hsc(m), hec(m), hh(hashes ? 32 * m : 0);
+  HIPCHK(hipMemcpyAsync(hsc.data(), dsc, m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(hec.data(), dec, m, hipMemcpyDeviceToHost, ctx->stream));
+  if (hashes) HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(sig_sync(ctx));
+  // the interpreter's order: OP_EQUALVERIFY, the encoding check, then the signature check
+  for (size_t k = 0; k < m; k++) {
+    const size_t i = P.items[k].slot;
+    // the hash the reference computes: check_signature reaches the checker with a key of 33 or 65 bytes and a
+    // signature that is not empty (interpreter.rs:18-30), whatever the key and the signature then parse to
+    const bool hashed = !(hsc[k] & (SC_F_EQUALVERIFY | SC_F_SIGNATURE_DER)) && srec[k].sig_len &&
+                        (srec[k].key_len == 33 || srec[k].key_len == 65);
+    status[i] = hsc[k] & SC_F_EQUALVERIFY ? ZG_INPUT_EQUALVERIFY : hsc[k] & SC_F_SIGNATURE_DER ? ZG_INPUT_SIGNATURE_DER
+              : hec[k] != ZG_ECDSA_OK ? ZG_INPUT_EVAL_FALSE : ZG_INPUT_OK;
+    if (detail && status[i] == ZG_INPUT_EVAL_FALSE) detail[i] = hec[k];
+    if (hashes && hashed) memcpy(hashes + 32 * i, hh.data() + 32 * k, 32);
+  }
   return ZG_OK;
 }
 

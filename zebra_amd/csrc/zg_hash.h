@@ -1,7 +1,8 @@
-// zg_hash.h -- the compression functions of SHA-256, SHA-512 (FIPS 180-4) and BLAKE2b (RFC 7693), once,
+// zg_hash.h -- the compression functions of SHA-256, SHA-512 (FIPS 180-4), BLAKE2b (RFC 7693) and
+// RIPEMD-160 (Dobbertin, Bosselaers, Preneel 1996), once,
 // as force-inlined host/device code on one lane. The callers keep what differs
 // between them: how the message words are gathered, the padding and the chaining over blocks
-// (zg_merkle.h, zg_equihash.hip, zg_sighash.h, zg_jubjub.h, zg_ed25519.h, zg_blake2b.h).
+// (zg_merkle.h, zg_equihash.hip, zg_sighash.h, zg_jubjub.h, zg_ed25519.h, zg_blake2b.h, zg_script.hip).
 // Every table is constexpr data indexed by unrolled loop counters, so no array is indexed by a run-time
 // value and the constants are immediates of the instructions (SHA-512's excepted, see there). Also
 // compiles as plain C++ (the host baseline of tools/bench_headers.py).
@@ -220,6 +221,83 @@ ZG_HASH_HD void blake2b_compress(uint64_t h[8], const uint64_t m[16], uint64_t t
 #undef ZG_B2_G
 #pragma unroll
   for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
+}
+
+// ---- RIPEMD-160: one compression chained on st (h0..h4). x: the 16 message words, little-endian values
+// (not clobbered). The two lines' word orders and rotation amounts are tables indexed by the unrolled
+// round counter; a rotation is one 32-bit funnel shift (v_alignbit_b32 with both operands the word).
+template <int K>
+ZG_HASH_HD uint32_t rmd_rotl(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbit(x, x, 32 - K);
+#else
+  return (x << K) | (x >> (32 - K));
+#endif
+}
+// f_j of round group G (0..4): the left line uses group j / 16, the right line 4 - j / 16
+template <int G>
+ZG_HASH_HD uint32_t rmd_f(uint32_t x, uint32_t y, uint32_t z) {
+  return G == 0 ? x ^ y ^ z : G == 1 ? (x & y) | (~x & z) : G == 2 ? (x | ~y) ^ z : G == 3 ? (x & z) | (y & ~z)
+                                                                                         : x ^ (y | ~z);
+}
+struct Rmd160Tables {
+  uint8_t rl[80], rr[80], sl[80], sr[80];
+};
+constexpr Rmd160Tables RMD160_T = {
+    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 7, 4, 13, 1, 10, 6, 15, 3, 12, 0, 9, 5, 2, 14, 11, 8,
+     3, 10, 14, 4, 9, 15, 8, 1, 2, 7, 0, 6, 13, 11, 5, 12, 1, 9, 11, 10, 0, 8, 12, 4, 13, 3, 7, 15, 14, 5, 6, 2,
+     4, 0, 5, 9, 7, 12, 2, 10, 14, 1, 3, 8, 11, 6, 15, 13},
+    {5, 14, 7, 0, 9, 2, 11, 4, 13, 6, 15, 8, 1, 10, 3, 12, 6, 11, 3, 7, 0, 13, 5, 10, 14, 15, 8, 12, 4, 9, 1, 2,
+     15, 5, 1, 3, 7, 14, 6, 9, 11, 8, 12, 2, 10, 0, 4, 13, 8, 6, 4, 1, 3, 11, 15, 0, 5, 12, 2, 13, 9, 7, 10, 14,
+     12, 15, 10, 4, 1, 5, 8, 7, 6, 2, 13, 14, 0, 3, 9, 11},
+    {11, 14, 15, 12, 5, 8, 7, 9, 11, 13, 14, 15, 6, 7, 9, 8, 7, 6, 8, 13, 11, 9, 7, 15, 7, 12, 15, 9, 11, 7, 13, 12,
+     11, 13, 6, 7, 14, 9, 13, 15, 14, 8, 13, 6, 5, 12, 7, 5, 11, 12, 14, 15, 14, 15, 9, 8, 9, 14, 5, 6, 8, 6, 5, 12,
+     9, 15, 5, 11, 6, 8, 13, 12, 5, 12, 13, 14, 11, 8, 5, 6},
+    {8, 9, 9, 11, 13, 15, 15, 5, 7, 7, 8, 11, 14, 14, 12, 6, 9, 13, 15, 7, 12, 8, 9, 11, 7, 7, 12, 7, 6, 15, 13, 11,
+     9, 7, 15, 11, 8, 6, 6, 14, 12, 13, 5, 14, 13, 13, 7, 5, 15, 5, 8, 11, 14, 14, 6, 14, 6, 9, 12, 9, 12, 5, 15, 8,
+     8, 5, 12, 9, 12, 5, 14, 6, 8, 13, 6, 5, 15, 13, 11, 11}};
+constexpr uint32_t RMD160_KL[5] = {0x00000000u, 0x5a827999u, 0x6ed9eba1u, 0x8f1bbcdcu, 0xa953fd4eu};
+constexpr uint32_t RMD160_KR[5] = {0x50a28be6u, 0x5c4dd124u, 0x6d703ef3u, 0x7a6d76e9u, 0x00000000u};
+
+// one step of a line: (a, b, c, d, e) <- (e, rotl_s(a + f(b, c, d) + x + k) + e, b, rotl_10(c), d)
+template <int G, int S>
+ZG_HASH_HD void rmd_step(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e, uint32_t x, uint32_t k) {
+  const uint32_t t = rmd_rotl<S>(a + rmd_f<G>(b, c, d) + x + k) + e;
+  a = e, e = d, d = rmd_rotl<10>(c), c = b, b = t;
+}
+// the 16 steps of round group G on both lines (J: the step within the group, counted down by recursion so
+// that the table entries are template arguments)
+template <int G, int J>
+struct RmdRound {
+  static ZG_HASH_HD void run(uint32_t* l, uint32_t* r, const uint32_t* x) {
+    constexpr int j = 16 * G + J;
+    rmd_step<G, RMD160_T.sl[j]>(l[0], l[1], l[2], l[3], l[4], x[RMD160_T.rl[j]], RMD160_KL[G]);
+    rmd_step<4 - G, RMD160_T.sr[j]>(r[0], r[1], r[2], r[3], r[4], x[RMD160_T.rr[j]], RMD160_KR[G]);
+    RmdRound<G, J + 1>::run(l, r, x);
+  }
+};
+template <int G>
+struct RmdRound<G, 16> {
+  static ZG_HASH_HD void run(uint32_t*, uint32_t*, const uint32_t*) {}
+};
+ZG_HASH_HD void ripemd160_iv(uint32_t st[5]) {
+  st[0] = 0x67452301u, st[1] = 0xefcdab89u, st[2] = 0x98badcfeu, st[3] = 0x10325476u, st[4] = 0xc3d2e1f0u;
+}
+ZG_HASH_HD void ripemd160_compress(uint32_t st[5], const uint32_t x[16]) {
+  uint32_t l[5], r[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) l[i] = r[i] = st[i];
+  RmdRound<0, 0>::run(l, r, x);
+  RmdRound<1, 0>::run(l, r, x);
+  RmdRound<2, 0>::run(l, r, x);
+  RmdRound<3, 0>::run(l, r, x);
+  RmdRound<4, 0>::run(l, r, x);
+  const uint32_t t = st[1] + l[2] + r[3];
+  st[1] = st[2] + l[3] + r[4];
+  st[2] = st[3] + l[4] + r[0];
+  st[3] = st[4] + l[0] + r[1];
+  st[4] = st[0] + l[1] + r[2];
+  st[0] = t;
 }
 
 }  // namespace zg

@@ -172,6 +172,7 @@ struct zg_ctx {
   zg::DevArena prep_arena;   // zg_prep_batch device buffers
   zg::DevArena tree_arena;   // zg_tree_roots scratch (zg_merkle.hip)
   zg::DevArena bn_arena;     // zg_pghr13_verify scratch (zg_pghr13.hip)
+  zg::DevArena inputs_arena; // zg_inputs_verify device buffers
   // the launch shape of zg_pghr13_verify's batch check (zg_pghr13.hip bn_pghr13_shape; zg_pghr13_shape reports it)
   int pghr_straus_b = 0;     // ZG_STRAUS_B: proofs per lane of k_pghr_straus, 1 / 2 / 4; 0 (any other value) by size
   int pghr_bseg_k = 0;       // ZG_BSEG_K: proofs per lane of k_pghr_bseg, 1..32 (larger: 32); 0 (or less) by size

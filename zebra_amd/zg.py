@@ -25,6 +25,13 @@ ECDSA_PUBKEY_STRIDE = 65
 TX_OK, TX_MALFORMED, TX_NONCANONICAL = 0, 1, 2
 SIGHASH_OK, SIGHASH_TX_MALFORMED, SIGHASH_TX_NONCANONICAL, SIGHASH_INPUT_RANGE = 0, 1, 2, 3
 SIGHASH_NO_INPUT = 0xFFFFFFFF
+# include/zg.h ZG_SCRIPT_* (zg_script_class: the template of a (script_sig, script_pubkey) pair; the one script flag a
+# template run reads) and ZG_INPUT_* (an item of zg_inputs_verify: the interpreter's error, or why there is no verdict)
+SCRIPT_HOST, SCRIPT_P2PKH, SCRIPT_P2PK = 0, 1, 2
+SCRIPT_VERIFY_DERSIG = 1
+(INPUT_OK, INPUT_EQUALVERIFY, INPUT_SIGNATURE_DER, INPUT_EVAL_FALSE, INPUT_HOST, INPUT_TX_MALFORMED,
+ INPUT_TX_NONCANONICAL, INPUT_RANGE) = range(8)
+INPUT_ERRORS = {INPUT_EQUALVERIFY: "EqualVerify", INPUT_SIGNATURE_DER: "SignatureDer", INPUT_EVAL_FALSE: "EvalFalse"}
 # include/zg.h ZG_EQ_* (Equihash instances), ZG_HDR_* (the first failing header check) and ZG_HDR_F_* (every check)
 EQ_200_9, EQ_96_5, EQ_48_5 = 0, 1, 2
 EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
@@ -107,6 +114,9 @@ def lib():
         L.zg_sighash.argtypes = [vp, sz, u8p, ctypes.POINTER(ctypes.c_uint64), u32p, sz, u32p, u32p, u8p, u32p,
                                  ctypes.POINTER(ctypes.c_uint64), u32p, u8p, u8p, u8p]
         u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.zg_script_class.argtypes = [u8p, sz, u8p, sz, u64p]
+        L.zg_inputs_verify.argtypes = [vp, sz, u8p, u64p, u32p, sz, u32p, u32p, u8p, u32p, u64p, ctypes.c_uint32, u8p,
+                                       u8p, u8p, u8p]
         L.zg_block_layout.argtypes = [u8p, sz, u64p, u64p, sz]
         L.zg_txids.argtypes = [vp, sz, u8p, u64p, u8p]
         L.zg_blocks_verify.argtypes = [vp, sz, u8p, u64p, ctypes.c_uint64, ctypes.c_uint64, sz, u8p, u8p, u64p, u8p,
@@ -297,6 +307,25 @@ def pack_sighash(txs, branch_ids, items):
     hashtype = (ctypes.c_uint32 * max(n, 1))(*[it[4] & 0xFFFFFFFF for it in items])
     return (b"".join(map(bytes, txs)), tx_off, branch, item_tx, index, b"".join(bytes(it[2]) for it in items),
             script_off, amount, hashtype)
+
+
+def script_class(script_sig, script_pubkey):
+    """zg_script_class: the template matcher zg_inputs_verify runs -> (SCRIPT_* class, signature push offset and
+    length in script_sig, key push offset and length: in script_sig for P2PKH, in script_pubkey for P2PK); all zero
+    for SCRIPT_HOST. CPU, no context"""
+    out = (ctypes.c_uint64 * 5)()
+    rc = lib().zg_script_class(bytes(script_sig) + b"\0", len(script_sig), bytes(script_pubkey) + b"\0",
+                               len(script_pubkey), out)
+    if rc < 0:
+        raise ZgError(rc, "zg_script_class")
+    return tuple(out)
+
+
+def pack_inputs_verify(txs, branch_ids, items):
+    """the buffers of zg_inputs_verify. items: (transaction number, input index, the spent output's script_pubkey,
+    its value) -> (arena, tx_off, branch, item_tx, input_index, prev_scripts, prev_off, amount), the arrays as ctypes"""
+    sh = pack_sighash(txs, branch_ids, [(t, i, s, a, 0) for t, i, s, a in items])
+    return sh[:8]
 
 
 def block_layout(raw):
@@ -575,6 +604,22 @@ class Context:
         self._chk(lib().zg_sighash(self._p, ntx, arena + b"\0", tx_off, branch, n, item_tx, index, scripts + b"\0",
                                    script_off, amount, hashtype, ts, hs, st))
         return list(ts.raw[:ntx]), [hs.raw[32 * i:32 * i + 32] for i in range(n)], list(st.raw[:n])
+
+    def inputs_verify(self, txs, branch_ids, items, flags=SCRIPT_VERIFY_DERSIG, want_detail=True, want_hashes=True):
+        """verify_script (script/src/interpreter.rs:288-360) of pay-to-pubkey-hash and pay-to-pubkey inputs over the
+        serialized transactions. items: (transaction number, input index, the spent output's script_pubkey, its
+        value) -> (TX_* per transaction, INPUT_* per item, the ECDSA_* detail of an EVAL_FALSE item or None, the
+        32-byte signature hash that was checked or None); INPUT_HOST: not a template, the caller runs the script"""
+        ntx, n = len(txs), len(items)
+        arena, tx_off, branch, item_tx, index, prev, prev_off, amount = pack_inputs_verify(txs, branch_ids, items)
+        ts = ctypes.create_string_buffer(max(ntx, 1))
+        st = ctypes.create_string_buffer(max(n, 1))
+        dt = ctypes.create_string_buffer(max(n, 1)) if want_detail else None
+        hs = ctypes.create_string_buffer(max(32 * n, 1)) if want_hashes else None
+        self._chk(lib().zg_inputs_verify(self._p, ntx, arena + b"\0", tx_off, branch, n, item_tx, index, prev + b"\0",
+                                         prev_off, amount, flags, ts, st, dt, hs))
+        return (list(ts.raw[:ntx]), list(st.raw[:n]), list(dt.raw[:n]) if want_detail else None,
+                [hs.raw[32 * i:32 * i + 32] for i in range(n)] if want_hashes else None)
 
     def txids(self, slices=None, arena=None, offsets=None):
         """dhash256 of each byte string (IndexedTransaction::hash), ONE call -> 32-byte hashes in H256 storage
