@@ -391,11 +391,57 @@ int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_o
  *        (the earlier checks passed, the key is 33 or 65 bytes, the signature push not empty), else zero.
  *        One kernel lane per template item reads the pushes in place, then the two kernels of zg_sighash and
  *        the kernel of zg_ecdsa_verify run on device-resident data; HOST, RANGE and TX_* items launch nothing.
- *        zg_last_sig_kernel_ms covers the kernels of this entry. */
+ *        zg_last_sig_kernel_ms covers the kernels of this entry.
+ *
+ * m-of-n OP_CHECKMULTISIG, bare or behind pay-to-script-hash, is evaluated as well where
+ * flags carries ZG_SCRIPT_TEMPLATE_MULTISIG; without the bit every output is what it is above, and bits 1 and 2
+ * stay ZG_E_INVAL. The acceptor always runs with verify_p2sh on (bip16_time is 0 on every network of
+ * network/src/consensus.rs) and with nulldummy, strictenc, sigpushonly, cleanstack and minimaldata off
+ * (verification/src/accept_transaction.rs:334-358).
+ *   zg_script_match <- zg_script_class, and with the bit in flags two more classes (CPU, no context; flags takes
+ *        the bits zg_inputs_verify takes):
+ *          ZG_SCRIPT_MULTISIG       script_pubkey = OP_m <key>...<key> OP_n ae; script_sig = one dummy push
+ *                                   instruction, then exactly m push instructions
+ *          ZG_SCRIPT_P2SH_MULTISIG  script_pubkey = a9 14 <20 bytes> 87 (is_pay_to_script_hash,
+ *                                   script/src/script.rs:131-136); script_sig = one dummy push, exactly m pushes,
+ *                                   then one push whose data is a script of the form above
+ *        OP_m and OP_n are the opcodes 51..60 with 1 <= m <= n <= 16, the key pushes number n and each is the
+ *        direct push 21 or 41 (any key bytes), push instructions are those of zg_script_class. Everything else
+ *        stays ZG_SCRIPT_HOST: OP_0 as m, counts given as data pushes, af, a signature push too few or too many,
+ *        a missing dummy, OP_1..OP_16 or OP_1NEGATE in script_sig, a redeem script that is P2PKH or P2PK or
+ *        longer than 520 bytes, a trailing byte. out[0] the class, out[1] m, out[2] n (1 and 1 for P2PKH and
+ *        P2PK), out[3..4] offset and length of the redeem script in script_sig (0, 0 for every other class),
+ *        out[5] the candidate pairs m (n - m + 1) (1 for P2PKH and P2PK), out[6] where the first signature push
+ *        instruction starts in script_sig, out[7] zero; all zero for HOST.
+ *   zg_inputs_verify with the bit, for an item of these two classes: verify_script (interpreter.rs:228-286)
+ *        evaluates script_sig, then script_pubkey; for P2SH it then pops the top push and evaluates it as a script
+ *        on the remaining stack. A redeem script whose dhash160 is not the script's 20 bytes leaves a false top:
+ *        EvalFalse, before the redeem script runs. OP_CHECKMULTISIG (interpreter.rs:786-840) pops n, the n keys,
+ *        m, the m signatures and one dummy element whose content is not checked; keys and signatures are held
+ *        in pop order, the last pushed first. Its walk keeps two indices s and k from 0 and runs while s < m and
+ *        success: check_signature_encoding on signature s (an empty push passes; under DERSIG a push that fails
+ *        is_valid_signature_encoding ends the script with SignatureDer), then check_signature
+ *        (interpreter.rs:12-31) on signature s and key k, the hashtype the signature's last byte, the script
+ *        code the script being evaluated, whole (the redeem script, or script_pubkey when bare; no
+ *        find_and_delete, no code-separator subscript); a passing check advances s, k always advances, then
+ *        success = m - s <= n - k. The result is [1] or the empty string, so a failed walk is EvalFalse. A
+ *        signature the walk never reaches is never encoding-checked.
+ *          ZG_INPUT_EVAL_FALSE     the hash mismatch (detail 0, hash zero) or a failed walk (detail: the
+ *                                  ZG_ECDSA_* status of the last pair checked)
+ *          ZG_INPUT_SIGNATURE_DER  the walk reaches a badly encoded push under DERSIG (detail 0, hash zero)
+ *          ZG_INPUT_OK             otherwise (detail 0)
+ *        hashes: the signature hash of the last pair the walk checked where the reference computes one (its
+ *        push is not empty), else zero. TX_*, RANGE and their precedence as above. On the device signature s
+ *        can only meet keys s .. s + (n - m), so every such pair is one row of the ECDSA kernel, which runs once
+ *        over the template rows and the pair rows, and a fold kernel replays the walk over the rows' statuses;
+ *        one signature hash is computed per signature push. More than 2^30 ECDSA rows in a call: ZG_E_INVAL. */
 #define ZG_SCRIPT_HOST 0
 #define ZG_SCRIPT_P2PKH 1
 #define ZG_SCRIPT_P2PK 2
+#define ZG_SCRIPT_MULTISIG 3
+#define ZG_SCRIPT_P2SH_MULTISIG 4
 #define ZG_SCRIPT_VERIFY_DERSIG 1
+#define ZG_SCRIPT_TEMPLATE_MULTISIG 256 /* 0x100 */
 #define ZG_INPUT_OK 0
 #define ZG_INPUT_EQUALVERIFY 1     /* Error::EqualVerify */
 #define ZG_INPUT_SIGNATURE_DER 2   /* Error::SignatureDer */
@@ -406,6 +452,8 @@ int zg_sighash(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_o
 #define ZG_INPUT_RANGE 7
 int zg_script_class(const uint8_t* script_sig, size_t sig_len, const uint8_t* script_pubkey, size_t pk_len,
                     uint64_t out[5]);
+int zg_script_match(const uint8_t* script_sig, size_t sig_len, const uint8_t* script_pubkey, size_t pk_len,
+                    uint32_t flags, uint64_t out[8]);
 int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
                      size_t n, const uint32_t* item_tx, const uint32_t* input_index, const uint8_t* prev_scripts,
                      const uint32_t* prev_off, const uint64_t* amount, uint32_t flags, uint8_t* tx_status,

@@ -84,7 +84,10 @@ pub const ZG_SIGHASH_NO_INPUT: u32 = 0xFFFF_FFFF;
 pub const ZG_SCRIPT_HOST: u8 = 0;
 pub const ZG_SCRIPT_P2PKH: u8 = 1;
 pub const ZG_SCRIPT_P2PK: u8 = 2;
+pub const ZG_SCRIPT_MULTISIG: u8 = 3;
+pub const ZG_SCRIPT_P2SH_MULTISIG: u8 = 4;
 pub const ZG_SCRIPT_VERIFY_DERSIG: u32 = 1;
+pub const ZG_SCRIPT_TEMPLATE_MULTISIG: u32 = 256;
 pub const ZG_INPUT_OK: u8 = 0;
 pub const ZG_INPUT_EQUALVERIFY: u8 = 1;
 pub const ZG_INPUT_SIGNATURE_DER: u8 = 2;
@@ -199,6 +202,8 @@ extern "C" {
                       hashes: *mut u8, status: *mut u8) -> c_int;
     pub fn zg_script_class(script_sig: *const u8, sig_len: usize, script_pubkey: *const u8, pk_len: usize,
                            out: *mut u64) -> c_int;
+    pub fn zg_script_match(script_sig: *const u8, sig_len: usize, script_pubkey: *const u8, pk_len: usize,
+                           flags: u32, out: *mut u64) -> c_int;
     pub fn zg_inputs_verify(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64, tx_branch_id: *const u32,
                             n: usize, item_tx: *const u32, input_index: *const u32, prev_scripts: *const u8,
                             prev_off: *const u32, amount: *const u64, flags: u32, tx_status: *mut u8,

@@ -79,6 +79,22 @@ pub fn script_class(script_sig: &[u8], script_pubkey: &[u8]) -> [u64; 5] {
     out
 }
 
+/// zg_script_match: script_class, and with ffi::ZG_SCRIPT_TEMPLATE_MULTISIG in `flags` the two multisig classes ->
+/// [class, m, n, offset and length of the redeem script in script_sig (0, 0 unless P2SH), candidate pairs
+/// m (n - m + 1), where the first signature push instruction starts in script_sig, 0]; all zero for ZG_SCRIPT_HOST.
+/// CPU, no context. An undefined flag bit is an error.
+pub fn script_match(script_sig: &[u8], script_pubkey: &[u8], flags: u32) -> Result<[u64; 8], GpuError> {
+    let mut out = [0u64; 8];
+    let pad = [0u8; 1];
+    let s = if script_sig.is_empty() { pad.as_ptr() } else { script_sig.as_ptr() };
+    let p = if script_pubkey.is_empty() { pad.as_ptr() } else { script_pubkey.as_ptr() };
+    let rc = unsafe { ffi::zg_script_match(s, script_sig.len(), p, script_pubkey.len(), flags, out.as_mut_ptr()) };
+    if rc < 0 {
+        return Err(GpuError { code: rc, message: "zg_script_match".to_string() });
+    }
+    Ok(out)
+}
+
 /// One batch slot on one GPU (device buffers only; the streams and the prepared verifying keys
 /// are shared per device inside libzg). Several slots keep several windows in flight.
 pub struct GpuVerifier {

@@ -33,7 +33,10 @@ handed in without their hash (Tx.ecdsa_requests: script code, hashtype and amoun
 are computed in ONE zg_sighash call before the signature batches. A transaction whose inputs are all pay-to-pubkey-hash
 or pay-to-pubkey spends (zg.script_class says so before any interpreter runs) needs no script run at all (SURVEY.md
 8(f) f15): it carries the outputs it spends (Tx.prevouts) instead of checks, and every such input of the window is
-verified -- HASH160, the encoding check, the signature hash and the signature -- in ONE zg_inputs_verify call. The
+verified -- HASH160, the encoding check, the signature hash and the signature -- in ONE zg_inputs_verify call. A
+window whose script_flags carry zg.SCRIPT_TEMPLATE_MULTISIG opts in to m-of-n OP_CHECKMULTISIG inputs as well, bare or
+behind pay-to-script-hash (zg.script_match names the class): the flags go to the call as they
+are. The
 collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
@@ -157,7 +160,8 @@ class Tx:
     branch_id: Optional[int] = None
     ecdsa_requests: List[EcdsaRequest] = field(default_factory=list)
     # the whole script check of template inputs on the GPU: one Prevout per input, set only when
-    # zg.script_class names every input of the transaction a template (P2PKH or P2PK). Needs raw and branch_id;
+    # zg.script_class names every input of the transaction a template (P2PKH or P2PK; with SCRIPT_TEMPLATE_MULTISIG in
+    # the window's script_flags, zg.script_match and the two multisig classes as well). Needs raw and branch_id;
     # ecdsa_checks, ecdsa_requests and eval_rerun must then be empty: no interpreter runs for this transaction
     prevouts: Optional[List[Prevout]] = None
 

@@ -12,6 +12,7 @@
 #include "zg_ed25519.h"  // ZG_ED_COMB_*
 #include "zg_inputs.h"
 #include "zg_jubjub.h"   // ZG_JJ_COMB_*
+#include "zg_multisig.h"
 #include "zg_prep.h"
 #include "zg_sighash.h"
 #include "zg_vk_embed.h"  // generated from zebra_amd/res/*.json by zebra_amd/build.py
@@ -37,6 +38,14 @@ hipError_t launch_sighash_items(hipStream_t st, const uint8_t* arena, const ShDe
 hipError_t launch_script_items(hipStream_t st, const uint8_t* arena, const uint8_t* prev, const ScDevItem* items, int n,
                                uint32_t flags, uint8_t* pubkeys, uint8_t* pubkey_len, uint8_t* sigs,
                                uint8_t* status);                                                   // zg_script.hip
+hipError_t launch_multisig_items(hipStream_t st, const uint8_t* arena, const uint8_t* prev, const MsDevItem* items, int n,
+                                 uint8_t* hash_bad);                                               // zg_multisig.hip
+hipError_t launch_multisig_rows(hipStream_t st, const uint8_t* arena, const uint8_t* prev, const MsDevItem* items,
+                                const MsDevSig* sigrec, int n, const uint8_t* hashes, uint8_t* pubkeys,
+                                uint8_t* pubkey_len, uint8_t* sigs, uint32_t* sig_off, uint8_t* msg, uint8_t* enc_bad);
+hipError_t launch_multisig_fold(hipStream_t st, const MsDevItem* items, const MsDevSig* sigrec, const uint32_t* sig_at,
+                                int n, const uint8_t* hash_bad, const uint8_t* enc_bad, const uint8_t* ec, uint32_t flags,
+                                uint8_t* status, uint8_t* detail, uint32_t* last);
 hipError_t launch_txid(hipStream_t st, const uint8_t* arena, const TxidSlice* slices, int n, uint8_t* out);  // zg_blocks.hip
 hipError_t launch_block_merkle(hipStream_t st, const uint8_t* arena, const MerkleBlk* blks, int nblk,
                                const uint8_t* ids, uint8_t* ping, uint8_t* pong, uint8_t* roots, uint8_t* match);
@@ -249,12 +258,14 @@ static std::array<size_t, 9> sh_dev_bytes(const ShPlan& P, size_t ntx, size_t ar
           sizeof(ShDevItem) * m, sizeof(uint32_t) * (P.in_off.size() + 1), sizeof(uint32_t) * (P.out_off.size() + 1),
           sizeof(uint32_t) * (P.jobs.size() + 1)};
 }
-// alloc(&pointer, bytes) -> hipError_t: the call's own allocations (zg_sighash) or parts of a context's arena
+// alloc(&pointer, bytes) -> hipError_t: the call's own allocations (zg_sighash) or parts of a context's arena.
+// tail: further script bytes, which follow `scripts` on the device (items index them from script_bytes on)
 template <class Alloc>
 static int sh_upload(zg_ctx* ctx, Alloc alloc, const ShPlan& P, size_t ntx, const uint8_t* arena, size_t arena_bytes,
-                     const uint8_t* scripts, size_t script_bytes, ShDev& D) {
+                     const uint8_t* scripts, size_t script_bytes, ShDev& D, const uint8_t* tail = nullptr,
+                     size_t tail_bytes = 0) {
   const size_t m = P.items.size();
-  const std::array<size_t, 9> b = sh_dev_bytes(P, ntx, arena_bytes, script_bytes);
+  const std::array<size_t, 9> b = sh_dev_bytes(P, ntx, arena_bytes, script_bytes + tail_bytes);
   HIPCHK(alloc(&D.arena, b[0]));
   HIPCHK(alloc(&D.scripts, b[1]));
   HIPCHK(alloc(&D.dig, b[2]));
@@ -266,6 +277,7 @@ static int sh_upload(zg_ctx* ctx, Alloc alloc, const ShPlan& P, size_t ntx, cons
   HIPCHK(alloc(&D.jobs, b[8]));
   HIPCHK(hipMemcpyAsync(D.arena, arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (script_bytes) HIPCHK(hipMemcpyAsync(D.scripts, scripts, script_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (tail_bytes) HIPCHK(hipMemcpyAsync(D.scripts + script_bytes, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(D.txs, P.dtx.data(), sizeof(ShDevTx) * ntx, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(D.items, P.items.data(), sizeof(ShDevItem) * m, hipMemcpyHostToDevice, ctx->stream));
   if (!P.in_off.empty())
@@ -350,7 +362,7 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
                                 uint8_t* detail, uint8_t* hashes) {
   if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status)) ||
       (n && (!item_tx || !input_index || !prev_scripts || !prev_off || !amount || !status)) || ntx > (1u << 30) ||
-      n > (1u << 30) || (flags & ~(uint32_t)ZG_SCRIPT_VERIFY_DERSIG))
+      n > (1u << 30) || (flags & ~(uint32_t)(ZG_SCRIPT_VERIFY_DERSIG | ZG_SCRIPT_TEMPLATE_MULTISIG)))
     return ZG_E_INVAL;
   if (!offsets_ok(tx_off, ntx, 1ull << 31) || !offsets_ok(prev_off, n, 0)) return ZG_E_INVAL;
   for (size_t i = 0; i < n; i++)
@@ -362,7 +374,15 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
   sh_plan_txs(P, ntx, txs, tx_off, tx_branch_id, tx_status);
   // the template inputs: the matcher validates every offset a lane of k_script_items follows
   const uint32_t prev0 = n ? prev_off[0] : 0;
+  const size_t prev_bytes = n ? (size_t)prev_off[n] - prev0 : 0;
   std::vector<ScDevItem> rec(n ? n : 1);
+  // the multisig items (zg_multisig.h): their records, the caller's item of each, their signature pushes as
+  // gathered, and the redeem scripts, which follow the previous scripts on the device as script codes
+  std::vector<MsDevItem> ms;
+  std::vector<uint32_t> ms_slot;
+  std::vector<MsDevSig> ms_sig;
+  std::vector<uint8_t> redeem;
+  uint64_t pair_rows = 0;
   P.items.reserve(n);
   for (size_t i = 0; i < n; i++) {
     const ShDevTx& d = P.dtx[item_tx[i]];
@@ -377,10 +397,32 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
     input_script_sig(tx, P.in_off.data() + d.L.in_idx, input_index[i], &so, &sl);
     const uint8_t* pk = prev_scripts + prev_off[i];
     const uint32_t pl = prev_off[i + 1] - prev_off[i];
-    const ScriptClass c = script_class(tx + so, sl, pk, pl);
-    if (c.cls == SCRIPT_HOST) continue;
+    const ScriptMatch sm = script_match(tx + so, sl, pk, pl, flags);
+    if (sm.cls == SCRIPT_HOST) continue;
     status[i] = ZG_INPUT_OK;
     const uint32_t poff = prev_off[i] - prev0;
+    if (sm.cls >= SCRIPT_MULTISIG) {
+      const bool p2sh = sm.cls == SCRIPT_P2SH_MULTISIG;
+      if (prev_bytes + redeem.size() + sm.red_len > 0xffffffffull)
+        return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: the script codes exceed 4 GiB");
+      // the script code: the script being evaluated, whole (interpreter.rs:814)
+      const uint32_t code_off = p2sh ? (uint32_t)(prev_bytes + redeem.size()) : poff, code_len = p2sh ? sm.red_len : pl;
+      if (p2sh) redeem.insert(redeem.end(), tx + so + sm.red_off, tx + so + sm.red_off + sm.red_len);
+      ms.push_back(MsDevItem{p2sh, sm.m, sm.n, p2sh ? d.base + so + sm.red_off + 1 : poff + 1, d.base + so + sm.red_off,
+                             sm.red_len, poff + 2, (uint32_t)ms_sig.size()});
+      ms_slot.push_back((uint32_t)i);
+      for (uint32_t s = 0; s < sm.m; s++) {  // pop order: the last pushed first
+        const uint32_t o = sm.sig_off[sm.m - 1 - s], l = sm.sig_len[sm.m - 1 - s];
+        // one signature hash per push; its slot, past the caller's items, names the push
+        sh_plan_add(P, ShDevItem{item_tx[i], input_index[i], code_off, code_len, l ? tx[so + o + l - 1] : 1u,
+                                 (uint32_t)(n + ms_sig.size()), amount[i]});
+        ms_sig.push_back(MsDevSig{(uint32_t)ms.size() - 1, s, d.base + so + o, l, 0, 0});
+      }
+      pair_rows += sm.pairs();
+      if (pair_rows > (1u << 30)) return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: more than 2^30 ECDSA rows");
+      continue;
+    }
+    const ScriptClass& c = sm.one;
     ScDevItem& r = rec[i];
     r.cls = c.cls;
     r.sig_off = d.base + so + c.sig_off, r.sig_len = c.sig_len;
@@ -395,17 +437,34 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
   sh_plan_finish(P, ntx);
   const size_t m = P.items.size();
   if (!m) return ZG_OK;  // HOST, range and transaction errors only: nothing is launched
+  // The planned items, dearest first within each part: the mt template items, whose ECDSA rows are rows 0 .. mt,
+  // then the ng signature pushes of the multisig items; the pair rows of push g follow those of push g - 1
+  const size_t ng = ms_sig.size(), mt = m - ng, nq = ms.size(), rows = mt + (size_t)pair_rows;
+  if (rows > (1u << 30)) return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: more than 2^30 ECDSA rows");
+  if (ng) std::stable_partition(P.items.begin(), P.items.end(), [&](const ShDevItem& it) { return it.slot < n; });
 
-  std::vector<ScDevItem> srec(m);
-  std::vector<uint32_t> sig_off(m + 1);
+  std::vector<ScDevItem> srec(mt);
+  std::vector<uint32_t> sig_off(mt + 1);
   uint64_t der_bytes = 0;  // (items may name one input many times: the sum is not bounded by the arena's size)
-  for (size_t k = 0; k < m; k++) {
+  for (size_t k = 0; k < mt; k++) {
     srec[k] = rec[P.items[k].slot];
     srec[k].der_off = sig_off[k] = (uint32_t)der_bytes;
     der_bytes += srec[k].sig_len ? srec[k].sig_len - 1 : 0;
     if (der_bytes > 0xffffffffull) return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: the signatures exceed 4 GiB");
   }
-  sig_off[m] = (uint32_t)der_bytes;
+  sig_off[mt] = (uint32_t)der_bytes;
+  std::vector<MsDevSig> gsig(ng);
+  std::vector<uint32_t> sig_at(ng), row_sig((size_t)pair_rows);  // (item, s) -> push; pair row -> push
+  for (size_t g = 0, row = 0; g < ng; g++) {
+    MsDevSig& r = gsig[g] = ms_sig[P.items[mt + g].slot - n];
+    const MsDevItem& q = ms[r.item];
+    const uint32_t per = q.n - q.m + 1;
+    r.row0 = (uint32_t)row, r.der0 = (uint32_t)der_bytes;
+    sig_at[q.sig0 + r.s] = (uint32_t)g;
+    for (uint32_t j = 0; j < per; j++) row_sig[row++] = (uint32_t)g;
+    der_bytes += (uint64_t)per * (r.sig_len ? r.sig_len - 1 : 0);
+    if (der_bytes > 0xffffffffull) return fail(ctx, ZG_E_INVAL, "zg_inputs_verify: the signatures exceed 4 GiB");
+  }
 
   HIPCHK(hipSetDevice(ctx->device));
   const uint32_t* comb = nullptr;
@@ -414,11 +473,15 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
   if (rc) return rc;
   // the context's arena (allocating per call costs more wall time than the kernels), every part 256-aligned
   const uint64_t base0 = tx_off[0];
-  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0), prev_bytes = (size_t)prev_off[n] - prev0;
-  const size_t own[7] = {sizeof(ScDevItem) * m, sizeof(uint32_t) * (m + 1), (size_t)ZG_ECDSA_PUBKEY_STRIDE * m, m,
-                         (size_t)der_bytes + 1, m, m};
+  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0);
+  // the template rows' parts, sized for the pair rows as well where k_ecdsa reads them; then the multisig parts:
+  // item and push records, sig_at, the messages of all rows, the hash and encoding flags, the fold's three outputs
+  const size_t own[16] = {sizeof(ScDevItem) * mt, sizeof(uint32_t) * (rows + 1), (size_t)ZG_ECDSA_PUBKEY_STRIDE * rows,
+                          rows, (size_t)der_bytes + 1, mt, rows,
+                          sizeof(MsDevItem) * nq, sizeof(MsDevSig) * ng, sizeof(uint32_t) * ng, ng ? 32 * rows : 0, nq, ng,
+                          nq, nq, sizeof(uint32_t) * nq};
   size_t need = 0;
-  for (size_t b : sh_dev_bytes(P, ntx, arena_bytes, prev_bytes)) need += Carve::span(b, 256);
+  for (size_t b : sh_dev_bytes(P, ntx, arena_bytes, prev_bytes + redeem.size())) need += Carve::span(b, 256);
   for (size_t b : own) need += Carve::span(b, 256);
   DevArena& A = ctx->inputs_arena;
   HIPCHK(A.reserve(need, ctx->stream));
@@ -427,7 +490,7 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
     using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
     *p = (T*)A.carve<uint8_t>(bytes, 256);  // (no part is empty: sh_dev_bytes)
     return hipSuccess;
-  }, P, ntx, txs + base0, arena_bytes, prev_scripts + prev0, prev_bytes, D);
+  }, P, ntx, txs + base0, arena_bytes, prev_scripts + prev0, prev_bytes, D, redeem.data(), redeem.size());
   if (rc) return rc;
   ScDevItem* const drec = (ScDevItem*)A.carve<uint8_t>(own[0], 256);
   uint32_t* const doff = (uint32_t*)A.carve<uint8_t>(own[1], 256);
@@ -436,21 +499,61 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
   uint8_t* const dsig = A.carve<uint8_t>(own[4], 256);
   uint8_t* const dsc = A.carve<uint8_t>(own[5], 256);
   uint8_t* const dec = A.carve<uint8_t>(own[6], 256);
-  HIPCHK(hipMemcpyAsync(drec, srec.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(doff, sig_off.data(), own[1], hipMemcpyHostToDevice, ctx->stream));
+  MsDevItem* const dms = (MsDevItem*)A.carve<uint8_t>(own[7], 256);
+  MsDevSig* const dgs = (MsDevSig*)A.carve<uint8_t>(own[8], 256);
+  uint32_t* const dat = (uint32_t*)A.carve<uint8_t>(own[9], 256);
+  uint8_t* const dmsg = A.carve<uint8_t>(own[10], 256);
+  uint8_t* const dhb = A.carve<uint8_t>(own[11], 256);
+  uint8_t* const denc = A.carve<uint8_t>(own[12], 256);
+  uint8_t* const dfs = A.carve<uint8_t>(own[13], 256);
+  uint8_t* const dfd = A.carve<uint8_t>(own[14], 256);
+  uint32_t* const dfl = (uint32_t*)A.carve<uint8_t>(own[15], 256);
+  if (mt) HIPCHK(hipMemcpyAsync(drec, srec.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(doff, sig_off.data(), sizeof(uint32_t) * (mt + 1), hipMemcpyHostToDevice, ctx->stream));
+  if (ng) {
+    HIPCHK(hipMemcpyAsync(dms, ms.data(), own[7], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dgs, gsig.data(), own[8], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dat, sig_at.data(), own[9], hipMemcpyHostToDevice, ctx->stream));
+  }
   HIPCHK(sig_timed(ctx, [&] {
-    hipError_t e = launch_script_items(ctx->stream, D.arena, D.scripts, drec, (int)m, flags, dpk, dlen, dsig, dsc);
+    hipError_t e = launch_script_items(ctx->stream, D.arena, D.scripts, drec, (int)mt, flags, dpk, dlen, dsig, dsc);
+    if (e == hipSuccess && ng) e = launch_multisig_items(ctx->stream, D.arena, D.scripts, dms, (int)nq, dhb);
     if (e == hipSuccess) e = sh_launch(ctx, P, D);
-    if (e == hipSuccess) e = launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, D.hash, (int)m, comb, dec);
+    if (!ng) return e != hipSuccess ? e : launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, D.hash, (int)mt, comb, dec);
+    // the messages of all rows in one buffer: the template rows' hashes, then what the pushes' lanes gather
+    if (e == hipSuccess && mt) e = hipMemcpyAsync(dmsg, D.hash, 32 * mt, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess)
+      e = launch_multisig_rows(ctx->stream, D.arena, D.scripts, dms, dgs, (int)ng, D.hash + 32 * mt,
+                               dpk + (size_t)ZG_ECDSA_PUBKEY_STRIDE * mt, dlen + mt, dsig, doff + mt, dmsg + 32 * mt, denc);
+    if (e == hipSuccess) e = launch_ecdsa(ctx->stream, dpk, dlen, dsig, doff, dmsg, (int)rows, comb, dec);
+    if (e == hipSuccess)
+      e = launch_multisig_fold(ctx->stream, dms, dgs, dat, (int)nq, dhb, denc, dec + mt, flags, dfs, dfd, dfl);
     return e;
   }));
-  std::vector<uint8_t> hsc(m), hec(m), hh(hashes ? 32 * m : 0);
-  HIPCHK(hipMemcpyAsync(hsc.data(), dsc, m, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(hec.data(), dec, m, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<uint8_t> hsc(mt), hec(mt), hh(hashes ? 32 * m : 0), hfs(nq), hfd(nq);
+  std::vector<uint32_t> hfl(nq);
+  if (mt) {
+    HIPCHK(hipMemcpyAsync(hsc.data(), dsc, mt, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hec.data(), dec, mt, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (ng) {
+    HIPCHK(hipMemcpyAsync(hfs.data(), dfs, nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hfd.data(), dfd, nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hfl.data(), dfl, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost, ctx->stream));
+  }
   if (hashes) HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * m, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(sig_sync(ctx));
+  // a multisig item: what the fold wrote; the hash is that of the last pair the walk checked, where the reference
+  // computes one (check_signature, interpreter.rs:23-30: the push is not empty)
+  for (size_t q = 0; q < nq; q++) {
+    const size_t i = ms_slot[q];
+    status[i] = hfs[q];
+    if (detail) detail[i] = hfd[q];
+    if (hashes && hfl[q] != MS_NO_PAIR && gsig[row_sig[hfl[q]]].sig_len)
+      memcpy(hashes + 32 * i, hh.data() + 32 * (mt + row_sig[hfl[q]]), 32);
+  }
   // the interpreter's order: OP_EQUALVERIFY, the encoding check, then the signature check
-  for (size_t k = 0; k < m; k++) {
+  for (size_t k = 0; k < mt; k++) {
     const size_t i = P.items[k].slot;
     // the hash the reference computes: check_signature reaches the checker with a key of 33 or 65 bytes and a
     // signature that is not empty (interpreter.rs:18-30), whatever the key and the signature then parse to

@@ -1,4 +1,4 @@
-// zg_script.h -- the two script templates zg_inputs_verify evaluates, host side
+// zg_script.h -- the script templates zg_inputs_verify evaluates, host side
 // (no HIP runtime: a stand-alone program includes it, like zg_txparse.h). Restates, for a pay-to-pubkey-hash
 // or pay-to-pubkey output spent by a script_sig of pushes only,
 //   verify_script / eval_script                     script/src/interpreter.rs:288-360, 361-1120
@@ -71,6 +71,69 @@ inline ScriptClass script_class(const uint8_t* sig, size_t sig_len, const uint8_
     return none;
   }
   return o == sig_len ? c : none;
+}
+
+// ---- m-of-n OP_CHECKMULTISIG, bare or behind pay-to-script-hash (the rules: include/zg.h)
+constexpr uint32_t SCRIPT_MULTISIG = 3, SCRIPT_P2SH_MULTISIG = 4;  // include/zg.h ZG_SCRIPT_*
+constexpr uint32_t SCRIPT_TEMPLATE_MULTISIG = 0x100;               // ZG_SCRIPT_TEMPLATE_MULTISIG
+constexpr uint32_t SCRIPT_MAX_KEYS = 16;                           // the counts are the opcodes OP_1..OP_16
+
+struct ScriptMatch {
+  uint32_t cls;
+  ScriptClass one;                 // P2PKH, P2PK: the record script_class gives
+  uint32_t m, n;                   // multisig: signatures and keys
+  uint32_t red_off, red_len;       // P2SH: the redeem script (the last push's data) in script_sig; bare: 0, 0
+  uint32_t sigs_at;                // where the first signature push instruction starts in script_sig, after the dummy
+  uint32_t sig_off[SCRIPT_MAX_KEYS], sig_len[SCRIPT_MAX_KEYS];  // the m signature pushes in script_sig, in push order
+  uint32_t pairs() const { return cls >= SCRIPT_MULTISIG ? m * (n - m + 1) : cls ? 1 : 0; }
+};
+
+// s[0..len) = OP_m <key>...<key> OP_n ae: OP_m and OP_n the opcodes 51..60, 1 <= m <= n, exactly n key pushes, each
+// the direct push 21 or 41 with its bytes inside the script, nothing after ae. The first key push is at s[1].
+inline bool script_multisig_form(const uint8_t* s, size_t len, uint32_t* m, uint32_t* n) {
+  if (len < 3 || s[0] < 0x51 || s[0] > 0x60) return false;
+  size_t o = 1;
+  uint32_t keys = 0;
+  while (o < len && (s[o] == 0x21 || s[o] == 0x41)) {
+    if (len - o < (size_t)s[o] + 1 || ++keys > SCRIPT_MAX_KEYS) return false;
+    o += (size_t)s[o] + 1;
+  }
+  if (len - o != 2 || s[o] < 0x51 || s[o] > 0x60 || s[o + 1] != 0xae) return false;
+  *m = s[0] - 0x50u, *n = s[o] - 0x50u;
+  return *n == keys && *m <= *n;
+}
+
+// script_class, and with SCRIPT_TEMPLATE_MULTISIG in flags the two multisig classes:
+//   MULTISIG:      script_pubkey of the form above; script_sig = <dummy> <sig> x m, push instructions, nothing else
+//   P2SH_MULTISIG: script_pubkey = a9 14 <20> 87; script_sig = <dummy> <sig> x m <redeem script of the form above>
+inline ScriptMatch script_match(const uint8_t* sig, size_t sig_len, const uint8_t* pk, size_t pk_len, uint32_t flags) {
+  ScriptMatch r{};
+  r.one = script_class(sig, sig_len, pk, pk_len);
+  r.cls = r.one.cls;
+  if (r.cls != SCRIPT_HOST) {
+    r.m = r.n = 1;
+    return r;
+  }
+  const ScriptMatch none = r;
+  if (!(flags & SCRIPT_TEMPLATE_MULTISIG)) return none;
+  const bool p2sh = pk_len == 23 && pk[0] == 0xa9 && pk[1] == 0x14 && pk[22] == 0x87;
+  if (!p2sh && !script_multisig_form(pk, pk_len, &r.m, &r.n)) return none;
+  // the pushes of script_sig: the dummy, at most 16 signatures, the redeem script
+  uint32_t off[SCRIPT_MAX_KEYS + 2], len[SCRIPT_MAX_KEYS + 2], np = 0;
+  size_t o = 0, second = 0;
+  while (o < sig_len) {
+    if (np == SCRIPT_MAX_KEYS + 2 || !script_push(sig, sig_len, &o, &off[np], &len[np])) return none;
+    if (!np++) second = o;
+  }
+  if (p2sh) {
+    if (np < 3 || !script_multisig_form(sig + off[np - 1], len[np - 1], &r.m, &r.n)) return none;
+    r.red_off = off[--np], r.red_len = len[np];
+  }
+  if (np != r.m + 1) return none;
+  for (uint32_t s = 0; s < r.m; s++) r.sig_off[s] = off[s + 1], r.sig_len[s] = len[s + 1];
+  r.sigs_at = (uint32_t)second;
+  r.cls = p2sh ? SCRIPT_P2SH_MULTISIG : SCRIPT_MULTISIG;
+  return r;
 }
 
 // is_valid_signature_encoding (interpreter.rs:49-136) over the n bytes of a signature push, hashtype byte

@@ -27,8 +27,9 @@ SIGHASH_OK, SIGHASH_TX_MALFORMED, SIGHASH_TX_NONCANONICAL, SIGHASH_INPUT_RANGE =
 SIGHASH_NO_INPUT = 0xFFFFFFFF
 # include/zg.h ZG_SCRIPT_* (zg_script_class: the template of a (script_sig, script_pubkey) pair; the one script flag a
 # template run reads) and ZG_INPUT_* (an item of zg_inputs_verify: the interpreter's error, or why there is no verdict)
-SCRIPT_HOST, SCRIPT_P2PKH, SCRIPT_P2PK = 0, 1, 2
+SCRIPT_HOST, SCRIPT_P2PKH, SCRIPT_P2PK, SCRIPT_MULTISIG, SCRIPT_P2SH_MULTISIG = 0, 1, 2, 3, 4
 SCRIPT_VERIFY_DERSIG = 1
+SCRIPT_TEMPLATE_MULTISIG = 0x100   # zg_inputs_verify evaluates the two multisig classes as well (opt-in)
 (INPUT_OK, INPUT_EQUALVERIFY, INPUT_SIGNATURE_DER, INPUT_EVAL_FALSE, INPUT_HOST, INPUT_TX_MALFORMED,
  INPUT_TX_NONCANONICAL, INPUT_RANGE) = range(8)
 INPUT_ERRORS = {INPUT_EQUALVERIFY: "EqualVerify", INPUT_SIGNATURE_DER: "SignatureDer", INPUT_EVAL_FALSE: "EvalFalse"}
@@ -115,6 +116,7 @@ def lib():
                                  ctypes.POINTER(ctypes.c_uint64), u32p, u8p, u8p, u8p]
         u64p = ctypes.POINTER(ctypes.c_uint64)
         L.zg_script_class.argtypes = [u8p, sz, u8p, sz, u64p]
+        L.zg_script_match.argtypes = [u8p, sz, u8p, sz, ctypes.c_uint32, u64p]
         L.zg_inputs_verify.argtypes = [vp, sz, u8p, u64p, u32p, sz, u32p, u32p, u8p, u32p, u64p, ctypes.c_uint32, u8p,
                                        u8p, u8p, u8p]
         L.zg_block_layout.argtypes = [u8p, sz, u64p, u64p, sz]
@@ -318,6 +320,18 @@ def script_class(script_sig, script_pubkey):
                                len(script_pubkey), out)
     if rc < 0:
         raise ZgError(rc, "zg_script_class")
+    return tuple(out)
+
+
+def script_match(script_sig, script_pubkey, flags=0):
+    """zg_script_match: script_class, and with SCRIPT_TEMPLATE_MULTISIG in `flags` the two multisig classes -> (SCRIPT_*
+    class, m, n, redeem script offset and length in script_sig (0, 0 unless P2SH), candidate pairs m (n - m + 1), where
+    the first signature push instruction starts in script_sig, 0); all zero for SCRIPT_HOST. CPU, no context"""
+    out = (ctypes.c_uint64 * 8)()
+    rc = lib().zg_script_match(bytes(script_sig) + b"\0", len(script_sig), bytes(script_pubkey) + b"\0",
+                               len(script_pubkey), flags, out)
+    if rc < 0:
+        raise ZgError(rc, "zg_script_match")
     return tuple(out)
 
 
@@ -609,7 +623,9 @@ class Context:
         """verify_script (script/src/interpreter.rs:288-360) of pay-to-pubkey-hash and pay-to-pubkey inputs over the
         serialized transactions. items: (transaction number, input index, the spent output's script_pubkey, its
         value) -> (TX_* per transaction, INPUT_* per item, the ECDSA_* detail of an EVAL_FALSE item or None, the
-        32-byte signature hash that was checked or None); INPUT_HOST: not a template, the caller runs the script"""
+        32-byte signature hash that was checked or None); INPUT_HOST: not a template, the caller runs the script. With
+        SCRIPT_TEMPLATE_MULTISIG in `flags`, m-of-n OP_CHECKMULTISIG inputs, bare or behind pay-to-script-hash, are
+        evaluated as well (script_match names the class): detail and hash are those of the last pair the walk checked"""
         ntx, n = len(txs), len(items)
         arena, tx_off, branch, item_tx, index, prev, prev_off, amount = pack_inputs_verify(txs, branch_ids, items)
         ts = ctypes.create_string_buffer(max(ntx, 1))
