@@ -459,6 +459,88 @@ int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t
                      const uint32_t* prev_off, const uint64_t* amount, uint32_t flags, uint8_t* tx_status,
                      uint8_t* status, uint8_t* detail, uint8_t* hashes);
 
+/* ---- shielded transactions from their bytes: for an import window, one call replaces
+ * JoinSplitVerification::check and SaplingProof::check (verification/src/accept_transaction.rs:575-596,649-657,
+ * 707-714): sprout::verify on the Groth16 branch (verification/src/sprout.rs:34-84) and accept_sapling
+ * (verification/src/sapling.rs:75-244), over the no-input signature hash the acceptor computes
+ * (accept_transaction.rs:374-387: hashtype 1, no script). The context's arena; zg_last_sig_kernel_ms covers the
+ * call's kernels outside the Groth16 batch pipeline.
+ *   zg_shielded_verify <- txs, tx_off, tx_branch_id as zg_sighash takes them, with its argument checks and
+ *        ntx = 0; all three verifying keys loaded, else ZG_E_NOVK as zg_batch_begin_device. Per transaction:
+ *          ZG_SHTX_OK                   a v4 transaction (Sapling version group) that passes. It always has
+ *                                       sapling = Some (chain/src/transaction.rs:291-303), so without spends and
+ *                                       outputs accept_sapling_final still runs, on the default binding_sig of 64
+ *                                       zero bytes and bvk = -[valueBalance] G_v: that passes for valueBalance 0
+ *                                       (the zero R has order 4 and the check multiplies by the cofactor) and
+ *                                       fails for any other value
+ *          ZG_SHTX_NONE                 v1..v3 without JoinSplits: join_split is None when the count is 0
+ *                                       (chain/src/join_split.rs:149-153), nothing is checked, the hash is zero
+ *          ZG_SHTX_JOINSPLIT_SIGNATURE  TransactionError::JoinSplitSignature: crypto::verify_ed25519 over the
+ *                                       hash fails (detail ZG_SHD_ED_*)
+ *          ZG_SHTX_INVALID_JOINSPLIT    TransactionError::InvalidJoinSplit(index): description index fails
+ *                                       sprout::verify (detail ZG_SHD_JOINSPLIT_ENCODING or _PROOF)
+ *          ZG_SHTX_INVALID_SAPLING      TransactionError::InvalidSapling: sapling::Error::Spend(index, ..),
+ *                                       Output(index, ..), InvalidBalanceValue or BadBindingSignature (detail)
+ *          ZG_SHTX_HOST                 v2 / v3 with JoinSplits: PHGR proofs over BN254, which stay with
+ *                                       zg_pghr13_verify and zg_ed25519_verify; nothing is launched for it and
+ *                                       its hash is zero
+ *          ZG_SHTX_TX_MALFORMED / _TX_NONCANONICAL  the transaction is (ZG_TX_*)
+ *        The status is the first error in the reference's order: the Ed25519 signature; the JoinSplit
+ *        descriptions in order; the spends in order, each cv, anchor, rk, spend_auth_sig, proof as accept_spend runs
+ *        them; the outputs in order, each cv, cmu, epk, proof; the balance value; the binding signature.
+ *        -> tx_status ntx (ZG_TX_*); status ntx; index ntx: the failing description's place in its own list (0
+ *        for the signatures and the balance value); detail ntx: ZG_SHD_*, the reference's inner error class;
+ *        hashes ntx x 32 (optional): the no-input signature hash of every v4 transaction, else zero; desc_off
+ *        ntx + 1 (optional; needed with desc_status) and desc_status, one byte per description (optional): the
+ *        descriptions of the window in the order JoinSplits, spends, outputs, transaction after transaction, each
+ *        byte that description's own first failing ZG_SHD_* whatever happened before it (as the flags of
+ *        zg_blocks_verify); a transaction that is not v4 has none.
+ *        Where the caller's checks go: tree_cache.continue_root of JoinSplit i follows sprout::verify of JoinSplit
+ *        i (accept_transaction.rs:575-592), so a tree error at description i wins over ZG_SHTX_INVALID_JOINSPLIT
+ *        with index > i and over every Sapling status, and loses to index <= i and to JOINSPLIT_SIGNATURE; the
+ *        JoinSplit nullifier check (accept_transaction.rs:655-656) follows the last description and precedes every
+ *        Sapling status; the Sapling nullifier check (accept_transaction.rs:737-741) follows ZG_SHTX_OK.
+ *        On the device: the arena goes up once; the hashes by the kernels of zg_sighash; one lane per description
+ *        gathers its fields, proof and value commitment in place and prepares a JoinSplit's nine inputs (hSig and
+ *        the 254-bit packing); the Sapling preparation, the binding keys, RedJubjub and Ed25519 by the kernels of
+ *        zg_prep_batch, zg_sapling_bvk, zg_redjubjub_verify and zg_ed25519_verify over the gathered rows; the
+ *        proofs by the context's batch pipeline over the rows where they are, max_batch at a time (a description
+ *        whose preparation failed enters with a device-written input count of 0: it comes back
+ *        ZG_STATUS_MALFORMED_VK and changes no other row); a fold kernel gives desc_status, then status, index
+ *        and detail; one download. A window without a v4 transaction launches nothing. More than 2^30
+ *        descriptions: ZG_E_INVAL. */
+#define ZG_SHTX_OK 0
+#define ZG_SHTX_NONE 1
+#define ZG_SHTX_JOINSPLIT_SIGNATURE 2
+#define ZG_SHTX_INVALID_JOINSPLIT 3
+#define ZG_SHTX_INVALID_SAPLING 4
+#define ZG_SHTX_HOST 5
+#define ZG_SHTX_TX_MALFORMED 6
+#define ZG_SHTX_TX_NONCANONICAL 7
+#define ZG_SHD_OK 0
+#define ZG_SHD_VALUE_COMMITMENT_INVALID 1      /* SpendError / OutputError::ValueCommitment(PointError::Invalid) */
+#define ZG_SHD_VALUE_COMMITMENT_SMALL_ORDER 2  /* ...::ValueCommitment(PointError::SmallOrder) */
+#define ZG_SHD_ANCHOR 3                        /* SpendError::Anchor */
+#define ZG_SHD_RANDOMIZED_KEY_INVALID 4        /* SpendError::RandomizedKey(PointError::Invalid) */
+#define ZG_SHD_RANDOMIZED_KEY_SMALL_ORDER 5    /* SpendError::RandomizedKey(PointError::SmallOrder) */
+#define ZG_SHD_NOTE_COMMITMENT 6               /* OutputError::NoteCommitment */
+#define ZG_SHD_EPHEMERAL_KEY_INVALID 7         /* OutputError::EphemeralKey(PointError::Invalid) */
+#define ZG_SHD_EPHEMERAL_KEY_SMALL_ORDER 8     /* OutputError::EphemeralKey(PointError::SmallOrder) */
+#define ZG_SHD_SPEND_AUTH_SIG 9                /* SpendError::BadSpendAuthSig */
+#define ZG_SHD_PROOF_INVALID 10                /* SpendError / OutputError::Proof(ProofError::Invalid) */
+#define ZG_SHD_PROOF_SYNTHESIS 11              /* ...::Proof(ProofError::Synthesis): not reachable with the built-in keys */
+#define ZG_SHD_PROOF_FAILED 12                 /* ...::Proof(ProofError::Failed) */
+#define ZG_SHD_BALANCE_VALUE 13                /* Error::InvalidBalanceValue: valueBalance is i64::MIN */
+#define ZG_SHD_BINDING_SIGNATURE 14            /* Error::BadBindingSignature */
+#define ZG_SHD_JOINSPLIT_ENCODING 15           /* ErrorKind::InvalidEncoding */
+#define ZG_SHD_JOINSPLIT_PROOF 16              /* ErrorKind::InvalidGrothProof */
+#define ZG_SHD_ED_PUBLIC_ENCODING 17           /* ZG_ED_PUBLIC_ENCODING */
+#define ZG_SHD_ED_SIGNATURE_ENCODING 18        /* ZG_ED_SIGNATURE_ENCODING */
+#define ZG_SHD_ED_SIGNATURE 19                 /* ZG_ED_SIGNATURE */
+int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
+                       uint8_t* tx_status, uint8_t* status, uint64_t* index, uint8_t* detail, uint8_t* hashes,
+                       uint64_t* desc_off, uint8_t* desc_status);
+
 /* ---- block bodies on the GPU: the transaction ids, the merkle root and the checks
  * of BlockVerifier::check, one call per import window. Device memory per call; n = 0 / nblk = 0 and the
  * argument checks as zg_headers_verify. zg_last_sig_kernel_ms covers the kernels of zg_txids and

@@ -96,6 +96,36 @@ pub const ZG_INPUT_HOST: u8 = 4;
 pub const ZG_INPUT_TX_MALFORMED: u8 = 5;
 pub const ZG_INPUT_TX_NONCANONICAL: u8 = 6;
 pub const ZG_INPUT_RANGE: u8 = 7;
+// zg_shielded_verify: a transaction's status (the reference's first error, or why there is no verdict) and the
+// inner error class (also a description's own first failing class)
+pub const ZG_SHTX_OK: u8 = 0;
+pub const ZG_SHTX_NONE: u8 = 1;
+pub const ZG_SHTX_JOINSPLIT_SIGNATURE: u8 = 2;
+pub const ZG_SHTX_INVALID_JOINSPLIT: u8 = 3;
+pub const ZG_SHTX_INVALID_SAPLING: u8 = 4;
+pub const ZG_SHTX_HOST: u8 = 5;
+pub const ZG_SHTX_TX_MALFORMED: u8 = 6;
+pub const ZG_SHTX_TX_NONCANONICAL: u8 = 7;
+pub const ZG_SHD_OK: u8 = 0;
+pub const ZG_SHD_VALUE_COMMITMENT_INVALID: u8 = 1;
+pub const ZG_SHD_VALUE_COMMITMENT_SMALL_ORDER: u8 = 2;
+pub const ZG_SHD_ANCHOR: u8 = 3;
+pub const ZG_SHD_RANDOMIZED_KEY_INVALID: u8 = 4;
+pub const ZG_SHD_RANDOMIZED_KEY_SMALL_ORDER: u8 = 5;
+pub const ZG_SHD_NOTE_COMMITMENT: u8 = 6;
+pub const ZG_SHD_EPHEMERAL_KEY_INVALID: u8 = 7;
+pub const ZG_SHD_EPHEMERAL_KEY_SMALL_ORDER: u8 = 8;
+pub const ZG_SHD_SPEND_AUTH_SIG: u8 = 9;
+pub const ZG_SHD_PROOF_INVALID: u8 = 10;
+pub const ZG_SHD_PROOF_SYNTHESIS: u8 = 11;
+pub const ZG_SHD_PROOF_FAILED: u8 = 12;
+pub const ZG_SHD_BALANCE_VALUE: u8 = 13;
+pub const ZG_SHD_BINDING_SIGNATURE: u8 = 14;
+pub const ZG_SHD_JOINSPLIT_ENCODING: u8 = 15;
+pub const ZG_SHD_JOINSPLIT_PROOF: u8 = 16;
+pub const ZG_SHD_ED_PUBLIC_ENCODING: u8 = 17;
+pub const ZG_SHD_ED_SIGNATURE_ENCODING: u8 = 18;
+pub const ZG_SHD_ED_SIGNATURE: u8 = 19;
 // zg_blocks_verify: the first failing check of BlockVerifier::check (after the parser's two verdicts), and
 // the flags of every check that fails
 pub const ZG_BLK_OK: u8 = 0;
@@ -208,6 +238,9 @@ extern "C" {
                             n: usize, item_tx: *const u32, input_index: *const u32, prev_scripts: *const u8,
                             prev_off: *const u32, amount: *const u64, flags: u32, tx_status: *mut u8,
                             status: *mut u8, detail: *mut u8, hashes: *mut u8) -> c_int;
+    pub fn zg_shielded_verify(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64, tx_branch_id: *const u32,
+                              tx_status: *mut u8, status: *mut u8, index: *mut u64, detail: *mut u8, hashes: *mut u8,
+                              desc_off: *mut u64, desc_status: *mut u8) -> c_int;
     pub fn zg_block_layout(block: *const u8, len: usize, out: *mut u64, tx_off: *mut u64, tx_off_cap: usize) -> c_int;
     pub fn zg_txids(ctx: *mut ZgCtx, n: usize, arena: *const u8, off: *const u64, hashes: *mut u8) -> c_int;
     pub fn zg_blocks_verify(ctx: *mut ZgCtx, nblk: usize, blocks: *const u8, blk_off: *const u64,

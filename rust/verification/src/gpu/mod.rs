@@ -381,6 +381,49 @@ impl GpuVerifier {
         Ok((tx_status, status, detail, hs))
     }
 
+    /// JoinSplitVerification::check and SaplingProof::check (accept_transaction.rs:575-596,649-657,707-714) of every
+    /// transaction of a window from its serialized bytes, ONE call. txs: (serialized transaction, consensus branch id)
+    /// -> per transaction (ffi::ZG_TX_*, ffi::ZG_SHTX_*: the reference's first error, the failing description's index
+    /// in its list, the ffi::ZG_SHD_* inner class, the no-input signature hash of a v4 transaction or zero) and, per
+    /// transaction, its descriptions' own ffi::ZG_SHD_* classes (JoinSplits, spends, outputs). ZG_SHTX_HOST: PHGR
+    /// JoinSplits, which stay with pghr13_verify and ed25519_verify. The caller keeps tree_cache.continue_root and the
+    /// nullifier checks; include/zg.h says where they go around the status.
+    pub fn shielded_verify(&self, txs: &[(Vec<u8>, u32)])
+                           -> Result<(Vec<u8>, Vec<u8>, Vec<u64>, Vec<u8>, Vec<[u8; 32]>, Vec<Vec<u8>>), GpuError> {
+        let _g = self.lock.lock().unwrap();
+        let ntx = txs.len();
+        let mut arena = Vec::new();
+        let mut tx_off = Vec::with_capacity(ntx + 1);
+        let mut branch = Vec::with_capacity(ntx + 1);
+        for (raw, b) in txs.iter() {
+            tx_off.push(arena.len() as u64);
+            arena.extend_from_slice(raw);
+            branch.push(*b);
+        }
+        tx_off.push(arena.len() as u64);
+        arena.push(0);
+        branch.push(0);
+        let mut tx_status = vec![0u8; ntx + 1];
+        let mut status = vec![0u8; ntx + 1];
+        let mut index = vec![0u64; ntx + 1];
+        let mut detail = vec![0u8; ntx + 1];
+        let mut hashes = vec![0u8; 32 * ntx + 1];
+        let mut desc_off = vec![0u64; ntx + 1];
+        let mut desc = vec![0u8; arena.len() / 384 + 1];   // a description takes at least 384 bytes of its transaction
+        check(self.ctx, unsafe {
+            ffi::zg_shielded_verify(self.ctx, ntx, arena.as_ptr(), tx_off.as_ptr(), branch.as_ptr(), tx_status.as_mut_ptr(),
+                                    status.as_mut_ptr(), index.as_mut_ptr(), detail.as_mut_ptr(), hashes.as_mut_ptr(),
+                                    desc_off.as_mut_ptr(), desc.as_mut_ptr())
+        })?;
+        tx_status.truncate(ntx);
+        status.truncate(ntx);
+        index.truncate(ntx);
+        detail.truncate(ntx);
+        let hs = (0..ntx).map(|i| { let mut h = [0u8; 32]; h.copy_from_slice(&hashes[32 * i..32 * i + 32]); h }).collect();
+        let ds = (0..ntx).map(|t| desc[desc_off[t] as usize..desc_off[t + 1] as usize].to_vec()).collect();
+        Ok((tx_status, status, index, detail, hs, ds))
+    }
+
     /// verify_equihash_solution (equihash.rs:80-172) for the instance `params` (ffi::ZG_EQ_*): per item
     /// (input, solution), inputs of one common length 1..=252 -> (ok, repeated) per item. `ok` is the
     /// reference's verdict, which accepts some solutions with a repeated index (distinct_indices,

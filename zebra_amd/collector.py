@@ -36,7 +36,12 @@ or pay-to-pubkey spends (zg.script_class says so before any interpreter runs) ne
 verified -- HASH160, the encoding check, the signature hash and the signature -- in ONE zg_inputs_verify call. A
 window whose script_flags carry zg.SCRIPT_TEMPLATE_MULTISIG opts in to m-of-n OP_CHECKMULTISIG inputs as well, bare or
 behind pay-to-script-hash (zg.script_match names the class): the flags go to the call as they
-are. The
+are. A transaction marked Tx.shielded carries no sliced fields at all: its whole JoinSplit and
+Sapling stage -- the hash, the Ed25519 signature, the JoinSplit and Sapling proofs with their preparation, the
+RedJubjub signatures -- is read from Tx.raw in ONE zg_shielded_verify call for the window, and the caller's tree and
+nullifier outcomes (Tx.tree_errors, js_nullifier_error, sapling_nullifier_error) are placed around its verdict. That
+call also checks the default binding signature of a v4 transaction without spends and outputs, as the reference does;
+the six-call path below does not. For every other transaction the
 collector prepares every public input of
 the window in one zg_prep_batch call (the Sapling descriptions' Jubjub decodes on the GPU, the
 JoinSplits on host threads; without a context, the per-description zg_prep_* host functions),
@@ -164,6 +169,12 @@ class Tx:
     # the window's script_flags, zg.script_match and the two multisig classes as well). Needs raw and branch_id;
     # ecdsa_checks, ecdsa_requests and eval_rerun must then be empty: no interpreter runs for this transaction
     prevouts: Optional[List[Prevout]] = None
+    # the whole JoinSplit and Sapling stage from the serialized bytes on the GPU, opt-in: with
+    # shielded set the transaction carries raw and branch_id, and js_pubkey, js_sig, joinsplits, spends, outputs,
+    # sighash and binding_sig stay empty -- nothing is sliced out on the host. The caller's tree_cache.continue_root
+    # outcomes go in tree_errors (one entry per JoinSplit description, None = ok; may be shorter than the list)
+    shielded: bool = False
+    tree_errors: List[Optional[str]] = field(default_factory=list)
 
 
 _POOL = None
@@ -376,7 +387,8 @@ def _resolve_sighashes(txs, ctx, sighash):
     the others are passed through untouched. resolve(i, input_index, script_code, hashtype) -> the sighash of
     a request of transaction i (computed by a further call if the window's did not hold it). A transaction
     or item the GPU does not hash (a status other than SIGHASH_OK) raises: the caller hashes it."""
-    need = [i for i, tx in enumerate(txs) if tx.raw is not None and (tx.sighash is None or tx.ecdsa_requests)]
+    need = [i for i, tx in enumerate(txs)
+            if tx.raw is not None and ((tx.sighash is None and not tx.shielded) or tx.ecdsa_requests)]
     bad = [i for i, tx in enumerate(txs) if tx.raw is None and tx.ecdsa_requests]
     if bad:
         raise zg.ZgError(-1, "transaction %d carries ecdsa_requests but no raw bytes" % bad[0])
@@ -402,7 +414,7 @@ def _resolve_sighashes(txs, ctx, sighash):
 
     pairs = []
     for i in need:
-        if txs[i].sighash is None:
+        if txs[i].sighash is None and not txs[i].shielded:
             pairs.append((i, (None, b"", 0, 1)))
         pairs += [(i, (r.input_index, bytes(r.script_code), r.amount, r.hashtype)) for r in txs[i].ecdsa_requests]
     known = {(i, it[0], it[1], it[3]): h for (i, it), h in zip(pairs, run(pairs))}
@@ -412,7 +424,7 @@ def _resolve_sighashes(txs, ctx, sighash):
         checks = list(tx.ecdsa_checks) + [
             EcdsaCheck(r.input_index, r.pubkey, r.sig, known[(i, r.input_index, bytes(r.script_code), r.hashtype)])
             for r in tx.ecdsa_requests]
-        out[i] = replace(tx, sighash=tx.sighash if tx.sighash is not None else known[(i, None, b"", 1)],
+        out[i] = replace(tx, sighash=tx.sighash if tx.sighash is not None else known.get((i, None, b"", 1)),
                          ecdsa_checks=checks)
 
     def resolve(i, input_index, script_code, hashtype):
@@ -504,10 +516,60 @@ def _input_errors(txs, ctx, inputs_verify, script_flags):
     return errors
 
 
+def _shielded_verdicts(txs, ctx, shielded_verify):
+    """-> {window index: (SHTX_* status, index)} of the transactions marked shielded, from ONE
+    shielded_verify(raws, branch_ids) call for the window (default ctx.shielded_verify). A transaction the GPU gives no
+    verdict on (PHGR JoinSplits, malformed or non-canonical bytes) raises: it is the caller's."""
+    need = [i for i, tx in enumerate(txs) if tx.shielded]
+    for i in need:
+        tx = txs[i]
+        if tx.raw is None or tx.branch_id is None:
+            raise ValueError("transaction %d is marked shielded but carries no raw bytes or no branch id" % i)
+        if (tx.joinsplits or tx.spends or tx.outputs or tx.js_pubkey is not None or tx.js_sig is not None
+                or tx.binding_sig is not None or tx.sighash is not None):
+            raise ValueError("transaction %d is marked shielded and carries proof or signature fields: its JoinSplit "
+                             "and Sapling stage is read from its bytes" % i)
+    if not need:
+        return {}
+    if shielded_verify is None:
+        if ctx is None:
+            raise zg.ZgError(-1, "transactions are marked shielded but no backend was given (pass ctx= or "
+                                 "shielded_verify=)")
+        shielded_verify = ctx.shielded_verify
+    res = shielded_verify([bytes(txs[i].raw) for i in need], [txs[i].branch_id for i in need])
+    out = {}
+    for k, i in enumerate(need):
+        st = res[1][k]
+        if st not in (zg.SHTX_OK, zg.SHTX_NONE) + tuple(zg.SHTX_ERRORS):
+            raise zg.ZgError(-1, "transaction %d: the shielded stage was not verified (ZG_SHTX status %d); check it "
+                                 "on the host" % (i, st))
+        out[i] = (st, res[2][k])
+    return out
+
+
+def _shielded_error(tx, verdict):
+    """the JoinSplit and Sapling stage of a transaction marked shielded: the GPU's first error with the caller's
+    outcomes at their places (accept_transaction.rs:575-596,649-657,737-741)"""
+    st, index = verdict
+    if st == zg.SHTX_JOINSPLIT_SIGNATURE:
+        return "JoinSplitSignature"
+    tree = next(((i, e) for i, e in enumerate(tx.tree_errors) if e), None)
+    if st == zg.SHTX_INVALID_JOINSPLIT and (tree is None or index <= tree[0]):
+        return ("InvalidJoinSplit", index)
+    if tree is not None:
+        return tree[1]
+    if tx.js_nullifier_error:
+        return tx.js_nullifier_error
+    if st == zg.SHTX_INVALID_SAPLING:
+        return "InvalidSapling"
+    return tx.sapling_nullifier_error
+
+
 def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig_ok=None, eval_error=None,
-              input_error=None):
+              input_error=None, shielded=None):
     """the reference's first error of one transaction, given the proof statuses; eval_error(tx) is asked
-    only when no earlier check failed. input_error: the eval error of a transaction of template inputs"""
+    only when no earlier check failed. input_error: the eval error of a transaction of template inputs;
+    shielded: the (status, index) of a transaction marked shielded"""
     if js_sig_ok is None:
         js_sig_ok = tx.js_sig_ok
     js_plan, sp_plan, out_plan = plan
@@ -523,6 +585,8 @@ def _tx_error(tx, plan, status, sp_ok=None, bind_ok=None, pghr_status=(), js_sig
         err = eval_error(tx)
         if err is not None:
             return err
+    if shielded is not None:
+        return _shielded_error(tx, shielded)
     if tx.joinsplits:
         if not js_sig_ok:
             return "JoinSplitSignature"
@@ -568,7 +632,7 @@ def _chunked(verify, cap):
 
 def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
                  verify_js_sigs=None, verify_ecdsa=None, sighash=None, inputs_verify=None,
-                 script_flags=zg.SCRIPT_VERIFY_DERSIG):
+                 script_flags=zg.SCRIPT_VERIFY_DERSIG, shielded_verify=None):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -594,8 +658,13 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     inputs are all templates (Tx.prevouts) have every input verified through inputs_verify(raws, branch_ids, items,
     flags) -> (tx statuses, statuses, ...), default ctx.inputs_verify (ONE zg_inputs_verify call for the window, made
     with script_flags: bip66_height is 0 on every network); their eval error stands where eval_rerun's does, and an
-    input the GPU gives no verdict on raises ZgError."""
+    input the GPU gives no verdict on raises ZgError. Transactions marked Tx.shielded have their whole JoinSplit and
+    Sapling stage read from their bytes through shielded_verify(raws, branch_ids) -> (tx statuses, SHTX_* statuses,
+    indices, ...), default ctx.shielded_verify (ONE zg_shielded_verify call for the window); the caller's tree_errors
+    and nullifier errors keep their places around its verdict, and a transaction it gives no verdict on raises
+    ZgError. Without the mark nothing changes."""
     input_errors = _input_errors(txs, ctx, inputs_verify, script_flags)
+    shielded = _shielded_verdicts(txs, ctx, shielded_verify)
     txs, resolve = _resolve_sighashes(txs, ctx, sighash)
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:
@@ -624,7 +693,7 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     eval_error = _eval_errors(txs, ctx, verify_ecdsa, resolve)
     for idx, (tx, plan) in enumerate(zip(txs, plans)):
         err = _tx_error(tx, plan, status, sp_ok[idx], bind_ok[idx], pghr_status, js_ok[idx], eval_error,
-                        input_errors.get(idx))
+                        input_errors.get(idx), shielded.get(idx))
         if err is not None:
             return idx, err
     return None

@@ -212,6 +212,7 @@ extern "C" zg_ctx* zg_create(const zg_config* cfg) {
 }
 
 static void set_state(zg_ctx* ctx, int st);
+static int batch_verdict_locked(zg_ctx* ctx, uint8_t* status, uint8_t* gt_out);
 
 extern "C" void zg_destroy(zg_ctx* ctx) {
   if (!ctx) return;
@@ -837,10 +838,8 @@ extern "C" int zg_batch_begin(zg_ctx* ctx, size_t n, const uint8_t* proofs, cons
   return batch_begin_locked(ctx, n, proofs, kinds, inputs, n_inputs, r);
 }
 
-extern "C" int zg_batch_begin_device(zg_ctx* ctx, size_t n, const void* d_proofs, const void* d_kinds,
+static int batch_begin_device_locked(zg_ctx* ctx, size_t n, const void* d_proofs, const void* d_kinds,
                                      const void* d_inputs, const void* d_n_inputs, const void* d_r) {
-  if (!ctx || (n && (!d_proofs || !d_kinds || !d_inputs))) return ZG_E_INVAL;
-  std::lock_guard<std::mutex> g(ctx->mu);
   HIPCHK(hipSetDevice(ctx->device));
   int rc = begin_common(ctx, n);
   if (rc) return rc;
@@ -865,6 +864,13 @@ extern "C" int zg_batch_begin_device(zg_ctx* ctx, size_t n, const void* d_proofs
   if ((rc = run_pipeline(ctx))) return rc;
   set_state(ctx, 1);
   return ZG_OK;
+}
+
+extern "C" int zg_batch_begin_device(zg_ctx* ctx, size_t n, const void* d_proofs, const void* d_kinds,
+                                     const void* d_inputs, const void* d_n_inputs, const void* d_r) {
+  if (!ctx || (n && (!d_proofs || !d_kinds || !d_inputs))) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return batch_begin_device_locked(ctx, n, d_proofs, d_kinds, d_inputs, d_n_inputs, d_r);
 }
 
 // check a list of tree nodes; mode per k_node_final. ok / out are host arrays (may be null).
@@ -1228,6 +1234,12 @@ extern "C" int zg_verify_batch(zg_ctx* ctx, size_t n, const uint8_t* proofs, con
   std::lock_guard<std::mutex> g(ctx->mu);
   int rc = batch_begin_locked(ctx, n, proofs, kinds, inputs, n_inputs, r);
   if (rc) return rc;
+  return batch_verdict_locked(ctx, status, gt_out);
+}
+
+// the batch that has begun, to its statuses: the root check, then zg_batch_finish's bisection where it failed
+static int batch_verdict_locked(zg_ctx* ctx, uint8_t* status, uint8_t* gt_out) {
+  int rc;
   if ((rc = settle_batch(ctx))) {
     set_state(ctx, 0);
     return rc;
@@ -1241,6 +1253,13 @@ extern "C" int zg_verify_batch(zg_ctx* ctx, size_t n, const uint8_t* proofs, con
     return rc;
   }
   return batch_finish_locked(ctx, okv[0], status, /*root_failed=*/okv[0] == 0);
+}
+
+// zg_host.h: zg_verify_batch over rows that are on the device already, read in place (zg_batch_begin_device)
+int zg::batch_verify_device_locked(zg_ctx* ctx, size_t n, const uint8_t* d_proofs, const uint8_t* d_kinds,
+                                   const uint8_t* d_inputs, const uint8_t* d_n_inputs, uint8_t* status) {
+  const int rc = batch_begin_device_locked(ctx, n, d_proofs, d_kinds, d_inputs, d_n_inputs, nullptr);
+  return rc ? rc : batch_verdict_locked(ctx, status, nullptr);
 }
 
 extern "C" int zg_last_timings(zg_ctx* ctx, float* ms7) { return zg_last_phase_ms(ctx, ms7, 7); }

@@ -14,6 +14,7 @@
 #include "zg_jubjub.h"   // ZG_JJ_COMB_*
 #include "zg_multisig.h"
 #include "zg_prep.h"
+#include "zg_shielded.h"
 #include "zg_sighash.h"
 #include "zg_vk_embed.h"  // generated from zebra_amd/res/*.json by zebra_amd/build.py
 
@@ -59,6 +60,17 @@ hipError_t launch_prep_sapling(hipStream_t st, const uint8_t* kinds, const uint8
 hipError_t launch_sapling_bvk(hipStream_t st, int ntx, const uint32_t* off, const uint32_t* nspends,
                               const uint8_t* cvs, const int64_t* vb, const uint32_t* comb, uint8_t* bvk,
                               uint8_t* status);
+hipError_t launch_shd_gather(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const ShdTx* stx,
+                             const ShdDesc* desc, int nd, uint8_t* kinds, uint8_t* fields, uint8_t* proofs,
+                             uint8_t* inputs, uint8_t* codes, uint8_t* cvs);                        // zg_shielded.hip
+hipError_t launch_shd_rows(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const ShdTx* stx, int ns,
+                           const ShdDesc* desc, int nd, const uint8_t* codes, const uint8_t* hashes,
+                           const uint8_t* bvk, uint8_t* ninputs, uint8_t* rj_vk, uint8_t* rj_sig, uint8_t* rj_msg,
+                           uint8_t* rj_gen, uint8_t* ed_pk, uint8_t* ed_sig, uint8_t* ed_msg);
+hipError_t launch_shd_fold(hipStream_t st, const ShDevTx* txs, const ShdTx* stx, int ns, const ShdDesc* desc, int nd,
+                           const uint8_t* codes, const uint8_t* rj_ok, const uint8_t* proof_status, const uint8_t* ed,
+                           const uint8_t* bvk_st, uint8_t* desc_status, uint8_t* status, uint32_t* index,
+                           uint8_t* detail);
 }  // namespace zg
 
 // ------------------------------------------------------------------ signature and header calls: shared pieces
@@ -564,6 +576,141 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
     if (detail && status[i] == ZG_INPUT_EVAL_FALSE) detail[i] = hec[k];
     if (hashes && hashed) memcpy(hashes + 32 * i, hh.data() + 32 * k, 32);
   }
+  return ZG_OK;
+}
+
+// ------------------------------------------------------------------ shielded transactions (zg_shielded.h)
+extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                                  const uint32_t* tx_branch_id, uint8_t* tx_status, uint8_t* status, uint64_t* index,
+                                  uint8_t* detail, uint8_t* hashes, uint64_t* desc_off, uint8_t* desc_status) {
+  if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status || !status || !index || !detail)) ||
+      ntx > (1u << 30) || (desc_status && !desc_off))
+    return ZG_E_INVAL;
+  if (!offsets_ok(tx_off, ntx, 1ull << 31)) return ZG_E_INVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (desc_off) desc_off[0] = 0;
+  if (!ntx) return ZG_OK;
+  for (int k = 0; k < ZG_NKINDS; k++)
+    if (!ctx->vk_loaded[k]) return fail(ctx, ZG_E_NOVK, "zg_shielded_verify needs all three verifying keys loaded");
+
+  ShPlan P;
+  sh_plan_txs(P, ntx, txs, tx_off, tx_branch_id, tx_status);
+  const uint64_t base0 = tx_off[0];
+  ShdPlan Q;
+  if (!shd_plan(P.dtx, ntx, txs + base0, tx_status, status, Q))
+    return fail(ctx, ZG_E_INVAL, "zg_shielded_verify: more than 2^30 descriptions");
+  const size_t ns = Q.stx.size(), nd = Q.desc.size(), nrj = Q.nrj, ned = Q.ned, ncv = Q.ncv();
+  for (size_t t = 0, s = 0; t < ntx; t++) {
+    index[t] = 0, detail[t] = 0;
+    if (hashes) memset(hashes + 32 * t, 0, 32);
+    if (desc_off) {
+      const bool here = s < ns && Q.stx[s].tx == t;
+      desc_off[t + 1] = here ? (s + 1 < ns ? Q.stx[s + 1].desc0 : nd) : desc_off[t];
+      s += here;
+    }
+  }
+  if (!ns) return ZG_OK;  // NONE, HOST and transaction errors only: nothing is launched
+  // the no-input hash the acceptor computes (accept_transaction.rs:374-387): hashtype 1, no script
+  P.items.reserve(ns);
+  for (size_t s = 0; s < ns; s++) sh_plan_add(P, ShDevItem{Q.stx[s].tx, ZG_SIGHASH_NO_INPUT, 0, 0, 1, (uint32_t)s, 0});
+  sh_plan_finish(P, ntx);
+  for (size_t k = 0; k < ns; k++) Q.stx[P.items[k].slot].hash = (uint32_t)k;
+
+  HIPCHK(hipSetDevice(ctx->device));
+  const uint32_t *jj = nullptr, *edc = nullptr;
+  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
+                      "Jubjub comb tables", &jj);
+  if (!rc && ned)
+    rc = comb_table(ctx, &ctx->dev->ed_comb, sizeof(uint32_t) * ZG_ED_COMB_WORDS * ZG_ED_COMB_POINTS, launch_ed_comb,
+                    "Ed25519 comb table", &edc);
+  if (rc) return rc;
+  // the context's arena, every part 256-aligned: the plan's records, the Groth16 rows of all descriptions, the
+  // value commitments and binding keys, the RedJubjub and Ed25519 rows, the verdicts
+  const size_t arena_bytes = (size_t)(tx_off[ntx] - base0);
+  const size_t own[26] = {sizeof(ShdTx) * ns, sizeof(ShdDesc) * nd, sizeof(uint32_t) * (ns + 1), sizeof(uint32_t) * ns,
+                          sizeof(int64_t) * ns, nd, (size_t)SHD_FIELD_BYTES * nd, 192 * nd, 288 * nd, nd, nd, 32 * ncv,
+                          32 * ns, ns, 32 * nrj, 64 * nrj, 64 * nrj, nrj, nrj, 32 * ned, 64 * ned, 32 * ned, ned,
+                          nd, nd, Carve::span(2 * ns, 4) + sizeof(uint32_t) * ns};
+  size_t need = 0;
+  for (size_t b : sh_dev_bytes(P, ntx, arena_bytes, 0)) need += Carve::span(b, 256);
+  for (size_t b : own) need += Carve::span(b, 256);
+  DevArena& A = ctx->shielded_arena;
+  HIPCHK(A.reserve(need, ctx->stream));
+  ShDev D;
+  rc = sh_upload(ctx, [&](auto** p, size_t bytes) {
+    using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
+    *p = (T*)A.carve<uint8_t>(bytes, 256);  // (no part is empty: sh_dev_bytes)
+    return hipSuccess;
+  }, P, ntx, txs + base0, arena_bytes, nullptr, 0, D);
+  if (rc) return rc;
+  size_t part = 0;
+  auto carve = [&] { return A.carve<uint8_t>(own[part++], 256); };
+  ShdTx* const dstx = (ShdTx*)carve();
+  ShdDesc* const ddesc = (ShdDesc*)carve();
+  uint32_t* const dcvoff = (uint32_t*)carve();
+  uint32_t* const dnsp = (uint32_t*)carve();
+  int64_t* const dvb = (int64_t*)carve();
+  uint8_t *const dkinds = carve(), *const dfields = carve(), *const dproofs = carve(), *const dinputs = carve();
+  uint8_t *const dcodes = carve(), *const dnin = carve(), *const dcvs = carve(), *const dbvk = carve();
+  uint8_t *const dbst = carve(), *const drjvk = carve(), *const drjsig = carve(), *const drjmsg = carve();
+  uint8_t *const drjgen = carve(), *const drjok = carve(), *const dedpk = carve(), *const dedsig = carve();
+  uint8_t *const dedmsg = carve(), *const dedst = carve(), *const dpst = carve(), *const ddst = carve();
+  uint8_t* const dres = carve();  // status and detail, a byte each per v4 transaction, then the indices
+  uint32_t* const dindex = (uint32_t*)(dres + Carve::span(2 * ns, 4));
+  HIPCHK(hipMemcpyAsync(dstx, Q.stx.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
+  if (nd) HIPCHK(hipMemcpyAsync(ddesc, Q.desc.data(), own[1], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dcvoff, Q.cv_off.data(), own[2], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dnsp, Q.nspend.data(), own[3], hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dvb, Q.vb.data(), own[4], hipMemcpyHostToDevice, ctx->stream));
+  // everything outside the Groth16 pipeline before it: the gather, the preparation, the hashes, the binding keys,
+  // the rows, the signatures
+  HIPCHK(sig_timed(ctx, [&] {
+    hipError_t e = launch_shd_gather(ctx->stream, D.arena, D.txs, dstx, ddesc, (int)nd, dkinds, dfields, dproofs, dinputs,
+                                     dcodes, dcvs);
+    if (e == hipSuccess && nd) e = launch_prep_sapling(ctx->stream, dkinds, dfields, (int)nd, dinputs, dcodes);
+    if (e == hipSuccess) e = sh_launch(ctx, P, D);
+    if (e == hipSuccess) e = launch_sapling_bvk(ctx->stream, (int)ns, dcvoff, dnsp, dcvs, dvb, jj, dbvk, dbst);
+    if (e == hipSuccess)
+      e = launch_shd_rows(ctx->stream, D.arena, D.txs, dstx, (int)ns, ddesc, (int)nd, dcodes, D.hash, dbvk, dnin, drjvk,
+                          drjsig, drjmsg, drjgen, dedpk, dedsig, dedmsg);
+    if (e == hipSuccess) e = launch_redjubjub(ctx->stream, drjvk, drjsig, drjmsg, drjgen, (int)nrj, jj, drjok);
+    if (e == hipSuccess && ned) e = launch_ed25519(ctx->stream, dedpk, dedsig, dedmsg, (int)ned, edc, dedst);
+    return e;
+  }));
+  // the context's own batch pipeline over the rows where they are, max_batch at a time; its statuses go back for
+  // the fold (a status does not depend on how the rows are grouped into batches)
+  std::vector<uint8_t> pst(nd + 1);
+  for (size_t o = 0; o < nd; o += ctx->cap) {
+    const size_t m = nd - o < ctx->cap ? nd - o : ctx->cap;
+    rc = batch_verify_device_locked(ctx, m, dproofs + 192 * o, dkinds + o, dinputs + 288 * o, dnin + o, &pst[o]);
+    if (rc) return rc;
+  }
+  float ms_before = 0.0f;
+  HIPCHK(hipEventSynchronize(ctx->sig_ev[1]));
+  HIPCHK(hipEventElapsedTime(&ms_before, ctx->sig_ev[0], ctx->sig_ev[1]));
+  if (nd) HIPCHK(hipMemcpyAsync(dpst, pst.data(), nd, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(sig_timed(ctx, [&] {
+    return launch_shd_fold(ctx->stream, D.txs, dstx, (int)ns, ddesc, (int)nd, dcodes, drjok, dpst, dedst, dbst, ddst, dres,
+                           dindex, dres + ns);
+  }));
+  // one download: the parts from the descriptions' statuses to the indices lie one after another in the arena
+  const size_t res_bytes = Carve::span(2 * ns, 4) + sizeof(uint32_t) * ns, dst_span = Carve::span(nd, 256);
+  std::vector<uint8_t> back(dst_span + res_bytes), hh(hashes ? 32 * ns : 0);
+  const uint8_t* const from = nd ? ddst : dres;
+  const size_t skip = nd ? dst_span : 0;
+  HIPCHK(hipMemcpyAsync(back.data(), from, skip + res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (hashes) HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * ns, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(sig_sync(ctx));
+  ctx->sig_ms += ms_before;
+  const uint8_t* res = back.data() + skip;
+  for (size_t s = 0; s < ns; s++) {
+    const size_t t = Q.stx[s].tx;
+    uint32_t ix;
+    memcpy(&ix, res + Carve::span(2 * ns, 4) + 4 * s, 4);
+    status[t] = res[s], detail[t] = res[ns + s], index[t] = ix;
+    if (hashes) memcpy(hashes + 32 * t, hh.data() + 32 * Q.stx[s].hash, 32);
+  }
+  if (desc_status && nd) memcpy(desc_status, back.data(), nd);
   return ZG_OK;
 }
 

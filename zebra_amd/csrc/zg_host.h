@@ -173,6 +173,7 @@ struct zg_ctx {
   zg::DevArena tree_arena;   // zg_tree_roots scratch (zg_merkle.hip)
   zg::DevArena bn_arena;     // zg_pghr13_verify scratch (zg_pghr13.hip)
   zg::DevArena inputs_arena; // zg_inputs_verify device buffers
+  zg::DevArena shielded_arena; // zg_shielded_verify device buffers
   // the launch shape of zg_pghr13_verify's batch check (zg_pghr13.hip bn_pghr13_shape; zg_pghr13_shape reports it)
   int pghr_straus_b = 0;     // ZG_STRAUS_B: proofs per lane of k_pghr_straus, 1 / 2 / 4; 0 (any other value) by size
   int pghr_bseg_k = 0;       // ZG_BSEG_K: proofs per lane of k_pghr_bseg, 1..32 (larger: 32); 0 (or less) by size
@@ -187,3 +188,10 @@ inline int fail(zg_ctx* c, int code, const std::string& msg) {
   c->err = msg;
   return code;
 }
+
+namespace zg {
+// zg.hip, for zg_shielded_verify: zg_verify_batch over rows on the device, read in place as zg_batch_begin_device
+// reads them (all three keys loaded, n <= max_batch); status on the host. The caller holds ctx->mu for the whole call
+int batch_verify_device_locked(zg_ctx* ctx, size_t n, const uint8_t* d_proofs, const uint8_t* d_kinds,
+                               const uint8_t* d_inputs, const uint8_t* d_n_inputs, uint8_t* status);
+}  // namespace zg

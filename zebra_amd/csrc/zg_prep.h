@@ -1,4 +1,4 @@
-// zg_prep.h -- host-side public-input preparation of the Groth16 checks (SURVEY.md 8(a)
+// zg_prep.h -- public-input preparation of the Groth16 checks (SURVEY.md 8(a)
 // rows a5-a7), in C++ over the same Fr arithmetic as the device code (zg_field.h, host path):
 //
 //   accept_spend   verification/src/sapling.rs:101-155  -> zg_prep_spend   (7 Fr)
@@ -251,16 +251,21 @@ ZG_HD inline int prep_output(const uint8_t* cv, const uint8_t* cmu, const uint8_
   return PREP_OK;
 }
 
-// hSig = BLAKE2b-256(personal "ZcashComputehSig"; random_seed || nf0 || nf1 || pubkey)
-inline void prep_hsig(const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf1, const uint8_t* pubkey,
-                      uint8_t* out) {
-  static const uint8_t personal[16] = {'Z', 'c', 'a', 's', 'h', 'C', 'o', 'm', 'p', 'u', 't', 'e', 'h', 'S', 'i', 'g'};
-  Blake2b h(32, personal);
-  h.update(seed, 32);
-  h.update(nf0, 32);
-  h.update(nf1, 32);
-  h.update(pubkey, 32);
-  h.final(out);
+// hSig = BLAKE2b-256(personal "ZcashComputehSig"; random_seed || nf0 || nf1 || pubkey): 128 bytes, one block.
+// Host and device (zg_shielded.h runs it on a lane); any byte alignment.
+ZG_HD inline void prep_hsig(const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf1, const uint8_t* pubkey,
+                            uint8_t* out) {
+  const uint8_t personal[16] = {'Z', 'c', 'a', 's', 'h', 'C', 'o', 'm', 'p', 'u', 't', 'e', 'h', 'S', 'i', 'g'};
+  uint64_t h[8], m[16];
+  blake2b_init(h, 32, blake2b_person(personal, 0), blake2b_person(personal, 1));
+  for (int w = 0; w < 16; w++) {
+    const uint8_t* p = (w < 4 ? seed : w < 8 ? nf0 : w < 12 ? nf1 : pubkey) + 8 * (w & 3);
+    uint64_t v = 0;
+    for (int b = 7; b >= 0; b--) v = (v << 8) | p[b];
+    m[w] = v;
+  }
+  blake2b_compress(h, m, 128, true);
+  for (int i = 0; i < 32; i++) out[i] = (uint8_t)(h[i / 8] >> (8 * (i % 8)));
 }
 
 // sprout.rs:42-58,86-153: the 2176-bit string (bytes MSB-first) of anchor, hSig, nf0, mac0,
@@ -268,27 +273,47 @@ inline void prep_hsig(const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf
 // read with its first bit as the least significant -> 9 field elements (32 B LE). chunk = 254
 // (bls::Fr::CAPACITY, into_bls_frs: the Groth16 branch) or 253 (into_bn_frs: the PHGR branch,
 // sprout.rs:119-133); either way a piece is < 2^254 and below the field's modulus.
+constexpr int PREP_JS_STREAM = 272;       // the string's bytes
+constexpr int PREP_JS_STREAM_PAD = 288;   // ... and the zero bytes prep_joinsplit_pack may read past them
+// out byte 32 c + j holds the string's bits chunk c + 8 j .. + 7, the first one lowest: a byte-wide window of two
+// neighbouring bytes, reversed. s: the string, zero from PREP_JS_STREAM to PREP_JS_STREAM_PAD
+ZG_HD inline void prep_joinsplit_pack(const uint8_t* s, int chunk, uint8_t* out) {
+  for (int c = 0; c < 9; c++)
+    for (int j = 0; j < 32; j++) {
+      const int p = chunk * c + 8 * j, q = p >> 3, r = p & 7, nb = chunk - 8 * j;
+      uint32_t v = ((((uint32_t)s[q] << 8) | s[q + 1]) >> (8 - r)) & 0xffu;
+      v = ((v & 0xf0u) >> 4) | ((v & 0x0fu) << 4);
+      v = ((v & 0xccu) >> 2) | ((v & 0x33u) << 2);
+      v = ((v & 0xaau) >> 1) | ((v & 0x55u) << 1);
+      if (nb < 8) v &= nb > 0 ? (1u << nb) - 1u : 0u;
+      out[32 * c + j] = (uint8_t)v;
+    }
+}
+ZG_HD inline void prep_joinsplit_bits(const uint8_t* anchor, const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf1,
+                                      const uint8_t* mac0, const uint8_t* mac1, const uint8_t* cm0, const uint8_t* cm1,
+                                      const uint8_t* vpub_old_le, const uint8_t* vpub_new_le, const uint8_t* pubkey,
+                                      int chunk, uint8_t* out) {
+  uint8_t s[PREP_JS_STREAM_PAD];
+  prep_hsig(seed, nf0, nf1, pubkey, s + 32);
+  for (int k = 0; k < 32; k++) {
+    s[k] = anchor[k];
+    s[64 + k] = nf0[k], s[96 + k] = mac0[k], s[128 + k] = nf1[k], s[160 + k] = mac1[k];
+    s[192 + k] = cm0[k], s[224 + k] = cm1[k];
+  }
+  for (int k = 0; k < 8; k++) s[256 + k] = vpub_old_le[k], s[264 + k] = vpub_new_le[k];
+  for (int k = PREP_JS_STREAM; k < PREP_JS_STREAM_PAD; k++) s[k] = 0;
+  prep_joinsplit_pack(s, chunk, out);
+}
 inline void prep_joinsplit_bits(const uint8_t* anchor, const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf1,
                                 const uint8_t* mac0, const uint8_t* mac1, const uint8_t* cm0, const uint8_t* cm1,
                                 uint64_t vpub_old, uint64_t vpub_new, const uint8_t* pubkey, int chunk,
                                 uint8_t* out) {
-  uint8_t hsig[32], vo[8], vn[8];
-  prep_hsig(seed, nf0, nf1, pubkey, hsig);
+  uint8_t vo[8], vn[8];
   for (int k = 0; k < 8; k++) {
     vo[k] = (uint8_t)(vpub_old >> (8 * k));
     vn[k] = (uint8_t)(vpub_new >> (8 * k));
   }
-  const uint8_t* parts[10] = {anchor, hsig, nf0, mac0, nf1, mac1, cm0, cm1, vo, vn};
-  const int lens[10] = {32, 32, 32, 32, 32, 32, 32, 32, 8, 8};
-  memset(out, 0, 9 * 32);
-  int bit = 0;
-  for (int p = 0; p < 10; p++)
-    for (int k = 0; k < lens[p]; k++)
-      for (int j = 7; j >= 0; j--, bit++)
-        if ((parts[p][k] >> j) & 1u) {
-          const int c = bit / chunk, pos = bit % chunk;
-          out[32 * c + pos / 8] |= (uint8_t)(1u << (pos % 8));
-        }
+  prep_joinsplit_bits(anchor, seed, nf0, nf1, mac0, mac1, cm0, cm1, vo, vn, pubkey, chunk, out);
 }
 
 inline void prep_joinsplit(const uint8_t* anchor, const uint8_t* seed, const uint8_t* nf0, const uint8_t* nf1,

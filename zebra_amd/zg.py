@@ -33,6 +33,17 @@ SCRIPT_TEMPLATE_MULTISIG = 0x100   # zg_inputs_verify evaluates the two multisig
 (INPUT_OK, INPUT_EQUALVERIFY, INPUT_SIGNATURE_DER, INPUT_EVAL_FALSE, INPUT_HOST, INPUT_TX_MALFORMED,
  INPUT_TX_NONCANONICAL, INPUT_RANGE) = range(8)
 INPUT_ERRORS = {INPUT_EQUALVERIFY: "EqualVerify", INPUT_SIGNATURE_DER: "SignatureDer", INPUT_EVAL_FALSE: "EvalFalse"}
+# include/zg.h ZG_SHTX_* (a transaction of zg_shielded_verify: the reference's first error, or why there is no verdict)
+# and ZG_SHD_* (the inner error class; a description's own first failing class)
+(SHTX_OK, SHTX_NONE, SHTX_JOINSPLIT_SIGNATURE, SHTX_INVALID_JOINSPLIT, SHTX_INVALID_SAPLING, SHTX_HOST,
+ SHTX_TX_MALFORMED, SHTX_TX_NONCANONICAL) = range(8)
+SHTX_ERRORS = {SHTX_JOINSPLIT_SIGNATURE: "JoinSplitSignature", SHTX_INVALID_JOINSPLIT: "InvalidJoinSplit",
+               SHTX_INVALID_SAPLING: "InvalidSapling"}
+(SHD_OK, SHD_VALUE_COMMITMENT_INVALID, SHD_VALUE_COMMITMENT_SMALL_ORDER, SHD_ANCHOR, SHD_RANDOMIZED_KEY_INVALID,
+ SHD_RANDOMIZED_KEY_SMALL_ORDER, SHD_NOTE_COMMITMENT, SHD_EPHEMERAL_KEY_INVALID, SHD_EPHEMERAL_KEY_SMALL_ORDER,
+ SHD_SPEND_AUTH_SIG, SHD_PROOF_INVALID, SHD_PROOF_SYNTHESIS, SHD_PROOF_FAILED, SHD_BALANCE_VALUE,
+ SHD_BINDING_SIGNATURE, SHD_JOINSPLIT_ENCODING, SHD_JOINSPLIT_PROOF, SHD_ED_PUBLIC_ENCODING,
+ SHD_ED_SIGNATURE_ENCODING, SHD_ED_SIGNATURE) = range(20)
 # include/zg.h ZG_EQ_* (Equihash instances), ZG_HDR_* (the first failing header check) and ZG_HDR_F_* (every check)
 EQ_200_9, EQ_96_5, EQ_48_5 = 0, 1, 2
 EQ_SOLUTION_BYTES = {EQ_200_9: 1344, EQ_96_5: 68, EQ_48_5: 36}
@@ -119,6 +130,7 @@ def lib():
         L.zg_script_match.argtypes = [u8p, sz, u8p, sz, ctypes.c_uint32, u64p]
         L.zg_inputs_verify.argtypes = [vp, sz, u8p, u64p, u32p, sz, u32p, u32p, u8p, u32p, u64p, ctypes.c_uint32, u8p,
                                        u8p, u8p, u8p]
+        L.zg_shielded_verify.argtypes = [vp, sz, u8p, u64p, u32p, u8p, u8p, u64p, u8p, u8p, u64p, u8p]
         L.zg_block_layout.argtypes = [u8p, sz, u64p, u64p, sz]
         L.zg_txids.argtypes = [vp, sz, u8p, u64p, u8p]
         L.zg_blocks_verify.argtypes = [vp, sz, u8p, u64p, ctypes.c_uint64, ctypes.c_uint64, sz, u8p, u8p, u64p, u8p,
@@ -309,6 +321,12 @@ def pack_sighash(txs, branch_ids, items):
     hashtype = (ctypes.c_uint32 * max(n, 1))(*[it[4] & 0xFFFFFFFF for it in items])
     return (b"".join(map(bytes, txs)), tx_off, branch, item_tx, index, b"".join(bytes(it[2]) for it in items),
             script_off, amount, hashtype)
+
+
+def pack_shielded(txs, branch_ids):
+    """the buffers of zg_shielded_verify. txs: serialized transactions; branch_ids: one consensus branch id per
+    transaction -> (arena, tx_off, branch), the arrays as ctypes"""
+    return pack_sighash(txs, branch_ids, [])[:3]
 
 
 def script_class(script_sig, script_pubkey):
@@ -636,6 +654,28 @@ class Context:
                                          prev_off, amount, flags, ts, st, dt, hs))
         return (list(ts.raw[:ntx]), list(st.raw[:n]), list(dt.raw[:n]) if want_detail else None,
                 [hs.raw[32 * i:32 * i + 32] for i in range(n)] if want_hashes else None)
+
+    def shielded_verify(self, txs, branch_ids, want_hashes=True, want_desc=True):
+        """JoinSplitVerification::check and SaplingProof::check (verification/src/accept_transaction.rs:575-596,
+        649-657,707-714) of every transaction of a window from its serialized bytes, ONE call -> (TX_* per transaction,
+        SHTX_* per transaction: the reference's first error, the failing description's index in its list, the SHD_*
+        inner class, the 32-byte no-input signature hash of a v4 transaction (zero otherwise) or None, per
+        transaction the list of its descriptions' own SHD_* classes (JoinSplits, spends, outputs) or None).
+        SHTX_HOST: PHGR JoinSplits, the caller keeps pghr13_verify and ed25519_verify for it"""
+        ntx = len(txs)
+        arena, tx_off, branch = pack_shielded(txs, branch_ids)
+        ts = ctypes.create_string_buffer(max(ntx, 1))
+        st = ctypes.create_string_buffer(max(ntx, 1))
+        dt = ctypes.create_string_buffer(max(ntx, 1))
+        ix = (ctypes.c_uint64 * max(ntx, 1))()
+        hs = ctypes.create_string_buffer(max(32 * ntx, 1)) if want_hashes else None
+        doff = (ctypes.c_uint64 * (ntx + 1))() if want_desc else None
+        # a description takes at least 384 bytes of its transaction
+        ds = ctypes.create_string_buffer(len(arena) // 384 + 1) if want_desc else None
+        self._chk(lib().zg_shielded_verify(self._p, ntx, arena + b"\0", tx_off, branch, ts, st, ix, dt, hs, doff, ds))
+        return (list(ts.raw[:ntx]), list(st.raw[:ntx]), list(ix[:ntx]), list(dt.raw[:ntx]),
+                [hs.raw[32 * i:32 * i + 32] for i in range(ntx)] if want_hashes else None,
+                [list(ds.raw[doff[t]:doff[t + 1]]) for t in range(ntx)] if want_desc else None)
 
     def txids(self, slices=None, arena=None, offsets=None):
         """dhash256 of each byte string (IndexedTransaction::hash), ONE call -> 32-byte hashes in H256 storage
