@@ -537,9 +537,42 @@ int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t
 #define ZG_SHD_ED_PUBLIC_ENCODING 17           /* ZG_ED_PUBLIC_ENCODING */
 #define ZG_SHD_ED_SIGNATURE_ENCODING 18        /* ZG_ED_SIGNATURE_ENCODING */
 #define ZG_SHD_ED_SIGNATURE 19                 /* ZG_ED_SIGNATURE */
+#define ZG_SHD_JOINSPLIT_PGHR_PROOF 20         /* ErrorKind::InvalidPGHRProof (ZG_SHIELDED_PHGR) */
 int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off, const uint32_t* tx_branch_id,
                        uint8_t* tx_status, uint8_t* status, uint64_t* index, uint8_t* detail, uint8_t* hashes,
                        uint64_t* desc_off, uint8_t* desc_status);
+/*   zg_shielded_verify_flags <- the same with flags; zg_shielded_verify is this entry with
+ *        flags = 0, down to the launches it makes. A bit outside ZG_SHIELDED_* is ZG_E_INVAL, before anything else.
+ *        ZG_SHIELDED_PHGR: a v2 / v3 transaction with JoinSplits is checked here instead of reported ZG_SHTX_HOST.
+ *        The call then also replaces the PHGR branch of sprout::verify (verification/src/sprout.rs:34-68),
+ *        Pghr13Proof::from_raw and verify (crypto/src/pghr13.rs:69-105) over the 1802-byte descriptions
+ *        (chain/src/join_split.rs:149-186), that is the four calls zg_sighash, zg_prep_batch with
+ *        ZG_PREP_KIND_JOINSPLIT_BN, zg_pghr13_verify and zg_ed25519_verify over host-sliced fields. Its status is the
+ *        first error in the reference's order, the Ed25519 signature, then the descriptions in order, where the
+ *        fold stops: a transaction before v4 has no balance value and no binding signature.
+ *          ZG_SHTX_OK, ZG_SHTX_JOINSPLIT_SIGNATURE (detail ZG_SHD_ED_*), ZG_SHTX_INVALID_JOINSPLIT with index and
+ *          detail ZG_SHD_JOINSPLIT_ENCODING (Pghr13Proof::from_raw fails: ZG_STATUS_DECODE_INVALID) or
+ *          ZG_SHD_JOINSPLIT_PGHR_PROOF (the proof does not verify). ZG_STATUS_INPUT_NONCANONICAL cannot occur: the
+ *          nine inputs are 253-bit chunks, below r; it would be reported as the proof's failure.
+ *        hashes: the no-input hash the acceptor computes for it (hashtype 1, no script): the Sprout form for a
+ *        transaction that is not overwintered, ZIP-143 under tx_branch_id for v3. desc_off and desc_status include
+ *        its descriptions, in the order stated above. ZG_SHTX_NONE, the malformed and non-canonical classes and
+ *        every v4 result are unchanged. The caller's tree_cache.continue_root and nullifier checks go where they
+ *        go for a v4 transaction's JoinSplits (above).
+ *        The BN254 key is the context's, the built-in key loaded on first use as zg_pghr13_verify does (only by a
+ *        window that has such a transaction); the ZG_E_NOVK rule for the three Groth16 keys holds whatever the
+ *        window contains. On the device: the PHGR descriptions are rows of their own, numbered apart from the Groth16
+ *        rows; one lane per description copies its 296-byte proof and writes its nine BN254 inputs (hSig and the
+ *        253-bit packing); the Ed25519 rows of these transactions follow the v4 ones' in one launch; the PGHR13
+ *        pipeline of zg_pghr13_verify runs over the rows where they are, ZG_PGHR_CHUNK at a time, after the Groth16
+ *        batches under the same lock, and leaves its statuses on the device, where a fold kernel (a lane per
+ *        transaction) reads them. zg_stats [8] and [9] count such a call as one PGHR13 call. A window whose flagged
+ *        transactions are all ZG_SHTX_NONE or errors launches nothing. */
+#define ZG_SHIELDED_PHGR 1u
+int zg_shielded_verify_flags(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                             const uint32_t* tx_branch_id, uint32_t flags, uint8_t* tx_status, uint8_t* status,
+                             uint64_t* index, uint8_t* detail, uint8_t* hashes, uint64_t* desc_off,
+                             uint8_t* desc_status);
 
 /* ---- block bodies on the GPU: the transaction ids, the merkle root and the checks
  * of BlockVerifier::check, one call per import window. Device memory per call; n = 0 / nblk = 0 and the
@@ -753,7 +786,7 @@ int zg_last_phase_ms(zg_ctx* ctx, float* ms, size_t n);
  * non-zero window digit, summed over the windows), [7] f-chain launches with four proofs per lane
  * (k_batch_fchain4; shards of 8,192 or more padded proofs -- ZG_QUAD_MIN -- or as ZG_FCHAIN_QUADS
  * forces), [8] zg_pghr13_verify calls with proofs (once per call, however many 65,536-proof chunks it
- * took), [9] those in which a chunk's batch check failed (that chunk then ran the per-proof check
+ * took) and zg_shielded_verify_flags calls with PHGR rows (once per call too), [9] those in which a chunk's batch check failed (that chunk then ran the per-proof check
  * for the exact statuses), [10] batches whose sums r_i C_i came
  * from the GLV products in decode and the C-sum tree (shards below 16,384 padded proofs -- ZG_K4_MIN
  * -- instead of K4's Pippenger buckets; [6] is 0 for them), [11] of the four-proofs-per-lane batches

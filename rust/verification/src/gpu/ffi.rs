@@ -126,6 +126,9 @@ pub const ZG_SHD_JOINSPLIT_PROOF: u8 = 16;
 pub const ZG_SHD_ED_PUBLIC_ENCODING: u8 = 17;
 pub const ZG_SHD_ED_SIGNATURE_ENCODING: u8 = 18;
 pub const ZG_SHD_ED_SIGNATURE: u8 = 19;
+pub const ZG_SHD_JOINSPLIT_PGHR_PROOF: u8 = 20;
+// zg_shielded_verify_flags: v2 / v3 transactions with PHGR JoinSplits are checked in the call
+pub const ZG_SHIELDED_PHGR: u32 = 1;
 // zg_blocks_verify: the first failing check of BlockVerifier::check (after the parser's two verdicts), and
 // the flags of every check that fails
 pub const ZG_BLK_OK: u8 = 0;
@@ -241,6 +244,10 @@ extern "C" {
     pub fn zg_shielded_verify(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64, tx_branch_id: *const u32,
                               tx_status: *mut u8, status: *mut u8, index: *mut u64, detail: *mut u8, hashes: *mut u8,
                               desc_off: *mut u64, desc_status: *mut u8) -> c_int;
+    pub fn zg_shielded_verify_flags(ctx: *mut ZgCtx, ntx: usize, txs: *const u8, tx_off: *const u64,
+                                    tx_branch_id: *const u32, flags: u32, tx_status: *mut u8, status: *mut u8,
+                                    index: *mut u64, detail: *mut u8, hashes: *mut u8, desc_off: *mut u64,
+                                    desc_status: *mut u8) -> c_int;
     pub fn zg_block_layout(block: *const u8, len: usize, out: *mut u64, tx_off: *mut u64, tx_off_cap: usize) -> c_int;
     pub fn zg_txids(ctx: *mut ZgCtx, n: usize, arena: *const u8, off: *const u64, hashes: *mut u8) -> c_int;
     pub fn zg_blocks_verify(ctx: *mut ZgCtx, nblk: usize, blocks: *const u8, blk_off: *const u64,

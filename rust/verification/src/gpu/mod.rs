@@ -390,6 +390,15 @@ impl GpuVerifier {
     /// nullifier checks; include/zg.h says where they go around the status.
     pub fn shielded_verify(&self, txs: &[(Vec<u8>, u32)])
                            -> Result<(Vec<u8>, Vec<u8>, Vec<u64>, Vec<u8>, Vec<[u8; 32]>, Vec<Vec<u8>>), GpuError> {
+        self.shielded_verify_flags(txs, 0)
+    }
+
+    /// The same with flags. ffi::ZG_SHIELDED_PHGR: a v2 / v3 transaction with JoinSplits is checked in the call too
+    /// (the Ed25519 signature, then Pghr13Proof::from_raw and verify per description: detail
+    /// ffi::ZG_SHD_JOINSPLIT_ENCODING or ffi::ZG_SHD_JOINSPLIT_PGHR_PROOF) instead of coming back ZG_SHTX_HOST; its
+    /// hash and its descriptions' classes are returned as a v4 transaction's are.
+    pub fn shielded_verify_flags(&self, txs: &[(Vec<u8>, u32)], flags: u32)
+                                 -> Result<(Vec<u8>, Vec<u8>, Vec<u64>, Vec<u8>, Vec<[u8; 32]>, Vec<Vec<u8>>), GpuError> {
         let _g = self.lock.lock().unwrap();
         let ntx = txs.len();
         let mut arena = Vec::new();
@@ -411,9 +420,10 @@ impl GpuVerifier {
         let mut desc_off = vec![0u64; ntx + 1];
         let mut desc = vec![0u8; arena.len() / 384 + 1];   // a description takes at least 384 bytes of its transaction
         check(self.ctx, unsafe {
-            ffi::zg_shielded_verify(self.ctx, ntx, arena.as_ptr(), tx_off.as_ptr(), branch.as_ptr(), tx_status.as_mut_ptr(),
-                                    status.as_mut_ptr(), index.as_mut_ptr(), detail.as_mut_ptr(), hashes.as_mut_ptr(),
-                                    desc_off.as_mut_ptr(), desc.as_mut_ptr())
+            ffi::zg_shielded_verify_flags(self.ctx, ntx, arena.as_ptr(), tx_off.as_ptr(), branch.as_ptr(), flags,
+                                          tx_status.as_mut_ptr(), status.as_mut_ptr(), index.as_mut_ptr(),
+                                          detail.as_mut_ptr(), hashes.as_mut_ptr(), desc_off.as_mut_ptr(),
+                                          desc.as_mut_ptr())
         })?;
         tx_status.truncate(ntx);
         status.truncate(ntx);

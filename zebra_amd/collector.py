@@ -516,10 +516,11 @@ def _input_errors(txs, ctx, inputs_verify, script_flags):
     return errors
 
 
-def _shielded_verdicts(txs, ctx, shielded_verify):
+def _shielded_verdicts(txs, ctx, shielded_verify, phgr=False):
     """-> {window index: (SHTX_* status, index)} of the transactions marked shielded, from ONE
     shielded_verify(raws, branch_ids) call for the window (default ctx.shielded_verify). A transaction the GPU gives no
-    verdict on (PHGR JoinSplits, malformed or non-canonical bytes) raises: it is the caller's."""
+    verdict on (PHGR JoinSplits, malformed or non-canonical bytes) raises: it is the caller's. phgr: the call is made
+    with phgr=True (ZG_SHIELDED_PHGR), and a v2 / v3 transaction with JoinSplits has its verdict from it."""
     need = [i for i, tx in enumerate(txs) if tx.shielded]
     for i in need:
         tx = txs[i]
@@ -536,7 +537,8 @@ def _shielded_verdicts(txs, ctx, shielded_verify):
             raise zg.ZgError(-1, "transactions are marked shielded but no backend was given (pass ctx= or "
                                  "shielded_verify=)")
         shielded_verify = ctx.shielded_verify
-    res = shielded_verify([bytes(txs[i].raw) for i in need], [txs[i].branch_id for i in need])
+    kw = {"phgr": True} if phgr else {}
+    res = shielded_verify([bytes(txs[i].raw) for i in need], [txs[i].branch_id for i in need], **kw)
     out = {}
     for k, i in enumerate(need):
         st = res[1][k]
@@ -632,7 +634,7 @@ def _chunked(verify, cap):
 
 def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None, verify_pghr=None,
                  verify_js_sigs=None, verify_ecdsa=None, sighash=None, inputs_verify=None,
-                 script_flags=zg.SCRIPT_VERIFY_DERSIG, shielded_verify=None):
+                 script_flags=zg.SCRIPT_VERIFY_DERSIG, shielded_verify=None, shielded_phgr=False):
     """Check the shielded proofs of a block (or an import window: a flat list of Tx in chain
     order). Returns None if every transaction passes, else (tx_index, error) with the error the
     reference reports (accept_chain.rs:79-80: the lowest failing index wins).
@@ -662,9 +664,11 @@ def verify_block(txs, verify=None, ctx=None, verify_sigs=None, sapling_bvk=None,
     Sapling stage read from their bytes through shielded_verify(raws, branch_ids) -> (tx statuses, SHTX_* statuses,
     indices, ...), default ctx.shielded_verify (ONE zg_shielded_verify call for the window); the caller's tree_errors
     and nullifier errors keep their places around its verdict, and a transaction it gives no verdict on raises
-    ZgError. Without the mark nothing changes."""
+    ZgError. With shielded_phgr that one call is made with phgr=True (ZG_SHIELDED_PHGR) and a
+    marked v2 / v3 transaction with PHGR JoinSplits is accepted: its Ed25519 signature and PGHR13 proofs are checked
+    in the call; without it such a transaction raises ZgError as before. Without the mark nothing changes."""
     input_errors = _input_errors(txs, ctx, inputs_verify, script_flags)
-    shielded = _shielded_verdicts(txs, ctx, shielded_verify)
+    shielded = _shielded_verdicts(txs, ctx, shielded_verify, shielded_phgr)
     txs, resolve = _resolve_sighashes(txs, ctx, sighash)
     items, pghr, plans = _queue(txs, ctx)
     if verify is None:

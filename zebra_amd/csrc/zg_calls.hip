@@ -71,6 +71,12 @@ hipError_t launch_shd_fold(hipStream_t st, const ShDevTx* txs, const ShdTx* stx,
                            const uint8_t* codes, const uint8_t* rj_ok, const uint8_t* proof_status, const uint8_t* ed,
                            const uint8_t* bvk_st, uint8_t* desc_status, uint8_t* status, uint32_t* index,
                            uint8_t* detail);
+hipError_t launch_shp_gather(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const ShpTx* ptx,
+                             const ShpDesc* desc, int nd, uint8_t* proofs, uint8_t* inputs);       // zg_shielded_phgr.hip
+hipError_t launch_shp_rows(hipStream_t st, const uint8_t* arena, const ShDevTx* txs, const ShpTx* ptx, int np,
+                           const uint8_t* hashes, uint8_t* ed_pk, uint8_t* ed_sig, uint8_t* ed_msg);
+hipError_t launch_shp_fold(hipStream_t st, const ShDevTx* txs, const ShpTx* ptx, int np, const uint8_t* proof_status,
+                           const uint8_t* ed, uint8_t* desc_status, uint8_t* status, uint32_t* index, uint8_t* detail);
 }  // namespace zg
 
 // ------------------------------------------------------------------ signature and header calls: shared pieces
@@ -580,11 +586,35 @@ extern "C" int zg_inputs_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, con
 }
 
 // ------------------------------------------------------------------ shielded transactions (zg_shielded.h)
-extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
-                                  const uint32_t* tx_branch_id, uint8_t* tx_status, uint8_t* status, uint64_t* index,
-                                  uint8_t* detail, uint8_t* hashes, uint64_t* desc_off, uint8_t* desc_status) {
+static int pghr13_load_locked(zg_ctx* ctx, const char* json, size_t len);
+static bool pghr13_rho(zg_ctx* ctx, size_t n, std::vector<uint8_t>& rho);
+
+// The PGHR13 pipeline over the npd gathered rows where they are, ctx->pghr_chunk at a time as zg_pghr13_verify
+// runs it, its scratch in ctx->bn_arena; the statuses stay on the device for the fold. One PGHR13 call in zg_stats.
+static int shielded_pghr13(zg_ctx* ctx, size_t npd, const uint8_t* dproofs, const uint8_t* dinputs, uint8_t* dstatus) {
+  std::vector<uint8_t> rho;
+  if (!pghr13_rho(ctx, npd, rho)) return fail(ctx, ZG_E_INVAL, "getrandom failed");
+  bool any_failed = false;
+  const size_t chunk = ctx->pghr_chunk;
+  for (size_t o = 0; o < npd; o += chunk) {
+    const size_t m = npd - o < chunk ? npd - o : chunk;
+    bool batch_failed = false;
+    const int rc = bn_pghr13_verify(ctx->bn_key, ctx->stream, ctx->side, m, ctx->pghr_straus_b, ctx->pghr_bseg_k,
+                                    dproofs + 296 * o, dinputs + 9 * 32 * o, nullptr, rho.data() + 80 * o, dstatus + o,
+                                    nullptr, &batch_failed, ctx->bn_arena, &ctx->err, true);
+    if (rc != ZG_OK) return rc;
+    any_failed = any_failed || batch_failed;
+  }
+  ctx->stats[8]++;
+  if (any_failed) ctx->stats[9]++;
+  return ZG_OK;
+}
+
+static int shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                           const uint32_t* tx_branch_id, uint32_t flags, uint8_t* tx_status, uint8_t* status,
+                           uint64_t* index, uint8_t* detail, uint8_t* hashes, uint64_t* desc_off, uint8_t* desc_status) {
   if (!ctx || (ntx && (!txs || !tx_off || !tx_branch_id || !tx_status || !status || !index || !detail)) ||
-      ntx > (1u << 30) || (desc_status && !desc_off))
+      ntx > (1u << 30) || (desc_status && !desc_off) || (flags & ~(uint32_t)ZG_SHIELDED_PHGR))
     return ZG_E_INVAL;
   if (!offsets_ok(tx_off, ntx, 1ull << 31)) return ZG_E_INVAL;
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -599,38 +629,54 @@ extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, c
   ShdPlan Q;
   if (!shd_plan(P.dtx, ntx, txs + base0, tx_status, status, Q))
     return fail(ctx, ZG_E_INVAL, "zg_shielded_verify: more than 2^30 descriptions");
-  const size_t ns = Q.stx.size(), nd = Q.desc.size(), nrj = Q.nrj, ned = Q.ned, ncv = Q.ncv();
-  for (size_t t = 0, s = 0; t < ntx; t++) {
+  // with ZG_SHIELDED_PHGR the transactions shd_plan left HOST: a plan of their own (np, npd: no effect on the v4 rows)
+  ShpPlan R;
+  if ((flags & ZG_SHIELDED_PHGR) && !shp_plan(P.dtx, ntx, Q.desc.size(), Q.ned, status, R))
+    return fail(ctx, ZG_E_INVAL, "zg_shielded_verify: more than 2^30 descriptions");
+  const size_t ns = Q.stx.size(), nd = Q.desc.size(), nrj = Q.nrj, ncv = Q.ncv();
+  const size_t np = R.ptx.size(), npd = R.desc.size(), ned = Q.ned + np, nsh = ns + np;
+  for (size_t t = 0; t < ntx; t++) {
     index[t] = 0, detail[t] = 0;
     if (hashes) memset(hashes + 32 * t, 0, 32);
-    if (desc_off) {
-      const bool here = s < ns && Q.stx[s].tx == t;
-      desc_off[t + 1] = here ? (s + 1 < ns ? Q.stx[s + 1].desc0 : nd) : desc_off[t];
-      s += here;
-    }
   }
-  if (!ns) return ZG_OK;  // NONE, HOST and transaction errors only: nothing is launched
-  // the no-input hash the acceptor computes (accept_transaction.rs:374-387): hashtype 1, no script
-  P.items.reserve(ns);
+  if (desc_off) shd_desc_offsets(Q, R, ntx, desc_off);
+  if (!nsh) return ZG_OK;  // NONE, HOST and transaction errors only: nothing is launched
+  // the no-input hash the acceptor computes (accept_transaction.rs:374-387): hashtype 1, no script; the slots of
+  // the transactions before v4 follow the v4 transactions'
+  P.items.reserve(nsh);
   for (size_t s = 0; s < ns; s++) sh_plan_add(P, ShDevItem{Q.stx[s].tx, ZG_SIGHASH_NO_INPUT, 0, 0, 1, (uint32_t)s, 0});
+  for (size_t q = 0; q < np; q++)
+    sh_plan_add(P, ShDevItem{R.ptx[q].tx, ZG_SIGHASH_NO_INPUT, 0, 0, 1, (uint32_t)(ns + q), 0});
   sh_plan_finish(P, ntx);
-  for (size_t k = 0; k < ns; k++) Q.stx[P.items[k].slot].hash = (uint32_t)k;
+  for (size_t k = 0; k < nsh; k++) {
+    const size_t slot = P.items[k].slot;
+    (slot < ns ? Q.stx[slot].hash : R.ptx[slot - ns].hash) = (uint32_t)k;
+  }
 
   HIPCHK(hipSetDevice(ctx->device));
+  int rc = ZG_OK;
+  if (npd && !ctx->bn_key)  // first use: the builtin key, as zg_pghr13_verify
+    rc = pghr13_load_locked(ctx, ZG_PGHR13_VK_JSON, strlen(ZG_PGHR13_VK_JSON));
+  if (rc) return rc;
   const uint32_t *jj = nullptr, *edc = nullptr;
-  int rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
-                      "Jubjub comb tables", &jj);
+  if (ns)
+    rc = comb_table(ctx, &ctx->dev->jj_comb, sizeof(uint32_t) * ZG_JJ_COMB_WORDS * ZG_JJ_COMB_POINTS, launch_jj_comb,
+                    "Jubjub comb tables", &jj);
   if (!rc && ned)
     rc = comb_table(ctx, &ctx->dev->ed_comb, sizeof(uint32_t) * ZG_ED_COMB_WORDS * ZG_ED_COMB_POINTS, launch_ed_comb,
                     "Ed25519 comb table", &edc);
   if (rc) return rc;
   // the context's arena, every part 256-aligned: the plan's records, the Groth16 rows of all descriptions, the
-  // value commitments and binding keys, the RedJubjub and Ed25519 rows, the verdicts
+  // value commitments and binding keys, the RedJubjub and Ed25519 rows, the verdicts; then the PHGR plan's records,
+  // its PGHR13 rows and verdicts (all empty without ZG_SHIELDED_PHGR)
   const size_t arena_bytes = (size_t)(tx_off[ntx] - base0);
-  const size_t own[26] = {sizeof(ShdTx) * ns, sizeof(ShdDesc) * nd, sizeof(uint32_t) * (ns + 1), sizeof(uint32_t) * ns,
+  const size_t pres_bytes = Carve::span(2 * np, 4) + sizeof(uint32_t) * np;
+  const size_t own[32] = {sizeof(ShdTx) * ns, sizeof(ShdDesc) * nd, sizeof(uint32_t) * (ns + 1), sizeof(uint32_t) * ns,
                           sizeof(int64_t) * ns, nd, (size_t)SHD_FIELD_BYTES * nd, 192 * nd, 288 * nd, nd, nd, 32 * ncv,
                           32 * ns, ns, 32 * nrj, 64 * nrj, 64 * nrj, nrj, nrj, 32 * ned, 64 * ned, 32 * ned, ned,
-                          nd, nd, Carve::span(2 * ns, 4) + sizeof(uint32_t) * ns};
+                          nd, nd, Carve::span(2 * ns, 4) + sizeof(uint32_t) * ns,
+                          sizeof(ShpTx) * np, sizeof(ShpDesc) * npd, (size_t)SHD_PHGR_PROOF_BYTES * npd, 288 * npd, npd,
+                          Carve::span(npd, 256) + pres_bytes};
   size_t need = 0;
   for (size_t b : sh_dev_bytes(P, ntx, arena_bytes, 0)) need += Carve::span(b, 256);
   for (size_t b : own) need += Carve::span(b, 256);
@@ -656,24 +702,39 @@ extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, c
   uint8_t *const drjgen = carve(), *const drjok = carve(), *const dedpk = carve(), *const dedsig = carve();
   uint8_t *const dedmsg = carve(), *const dedst = carve(), *const dpst = carve(), *const ddst = carve();
   uint8_t* const dres = carve();  // status and detail, a byte each per v4 transaction, then the indices
-  uint32_t* const dindex = (uint32_t*)(dres + Carve::span(2 * ns, 4));
-  HIPCHK(hipMemcpyAsync(dstx, Q.stx.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
-  if (nd) HIPCHK(hipMemcpyAsync(ddesc, Q.desc.data(), own[1], hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dcvoff, Q.cv_off.data(), own[2], hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dnsp, Q.nspend.data(), own[3], hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(dvb, Q.vb.data(), own[4], hipMemcpyHostToDevice, ctx->stream));
-  // everything outside the Groth16 pipeline before it: the gather, the preparation, the hashes, the binding keys,
-  // the rows, the signatures
+  uint32_t* const dindex = dres ? (uint32_t*)(dres + Carve::span(2 * ns, 4)) : nullptr;
+  ShpTx* const dptx = (ShpTx*)carve();
+  ShpDesc* const dpdesc = (ShpDesc*)carve();
+  uint8_t *const dpgproofs = carve(), *const dpginputs = carve(), *const dpgst = carve();
+  uint8_t* const dpdst = carve();  // the PHGR descriptions' classes, then status, detail and the indices as dres
+  uint8_t* const dpres = dpdst ? dpdst + Carve::span(npd, 256) : nullptr;
+  uint32_t* const dpindex = dpres ? (uint32_t*)(dpres + Carve::span(2 * np, 4)) : nullptr;
+  if (ns) {
+    HIPCHK(hipMemcpyAsync(dstx, Q.stx.data(), own[0], hipMemcpyHostToDevice, ctx->stream));
+    if (nd) HIPCHK(hipMemcpyAsync(ddesc, Q.desc.data(), own[1], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dcvoff, Q.cv_off.data(), own[2], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dnsp, Q.nspend.data(), own[3], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dvb, Q.vb.data(), own[4], hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (np) {
+    HIPCHK(hipMemcpyAsync(dptx, R.ptx.data(), own[26], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dpdesc, R.desc.data(), own[27], hipMemcpyHostToDevice, ctx->stream));
+  }
+  // everything outside the proof pipelines before them: the gathers, the preparation, the hashes, the binding keys,
+  // the rows, the signatures (one Ed25519 launch: the rows of the transactions before v4 follow the v4 ones')
   HIPCHK(sig_timed(ctx, [&] {
-    hipError_t e = launch_shd_gather(ctx->stream, D.arena, D.txs, dstx, ddesc, (int)nd, dkinds, dfields, dproofs, dinputs,
-                                     dcodes, dcvs);
+    hipError_t e = hipSuccess;
+    if (ns) e = launch_shd_gather(ctx->stream, D.arena, D.txs, dstx, ddesc, (int)nd, dkinds, dfields, dproofs, dinputs,
+                                  dcodes, dcvs);
     if (e == hipSuccess && nd) e = launch_prep_sapling(ctx->stream, dkinds, dfields, (int)nd, dinputs, dcodes);
+    if (e == hipSuccess) e = launch_shp_gather(ctx->stream, D.arena, D.txs, dptx, dpdesc, (int)npd, dpgproofs, dpginputs);
     if (e == hipSuccess) e = sh_launch(ctx, P, D);
-    if (e == hipSuccess) e = launch_sapling_bvk(ctx->stream, (int)ns, dcvoff, dnsp, dcvs, dvb, jj, dbvk, dbst);
-    if (e == hipSuccess)
+    if (e == hipSuccess && ns) e = launch_sapling_bvk(ctx->stream, (int)ns, dcvoff, dnsp, dcvs, dvb, jj, dbvk, dbst);
+    if (e == hipSuccess && ns)
       e = launch_shd_rows(ctx->stream, D.arena, D.txs, dstx, (int)ns, ddesc, (int)nd, dcodes, D.hash, dbvk, dnin, drjvk,
                           drjsig, drjmsg, drjgen, dedpk, dedsig, dedmsg);
-    if (e == hipSuccess) e = launch_redjubjub(ctx->stream, drjvk, drjsig, drjmsg, drjgen, (int)nrj, jj, drjok);
+    if (e == hipSuccess) e = launch_shp_rows(ctx->stream, D.arena, D.txs, dptx, (int)np, D.hash, dedpk, dedsig, dedmsg);
+    if (e == hipSuccess && ns) e = launch_redjubjub(ctx->stream, drjvk, drjsig, drjmsg, drjgen, (int)nrj, jj, drjok);
     if (e == hipSuccess && ned) e = launch_ed25519(ctx->stream, dedpk, dedsig, dedmsg, (int)ned, edc, dedst);
     return e;
   }));
@@ -685,21 +746,31 @@ extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, c
     rc = batch_verify_device_locked(ctx, m, dproofs + 192 * o, dkinds + o, dinputs + 288 * o, dnin + o, &pst[o]);
     if (rc) return rc;
   }
+  // the PGHR13 pipeline over its rows where they are; its statuses stay on the device for the fold
+  if (npd) {
+    rc = shielded_pghr13(ctx, npd, dpgproofs, dpginputs, dpgst);
+    if (rc) return rc;
+  }
   float ms_before = 0.0f;
   HIPCHK(hipEventSynchronize(ctx->sig_ev[1]));
   HIPCHK(hipEventElapsedTime(&ms_before, ctx->sig_ev[0], ctx->sig_ev[1]));
   if (nd) HIPCHK(hipMemcpyAsync(dpst, pst.data(), nd, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(sig_timed(ctx, [&] {
-    return launch_shd_fold(ctx->stream, D.txs, dstx, (int)ns, ddesc, (int)nd, dcodes, drjok, dpst, dedst, dbst, ddst, dres,
-                           dindex, dres + ns);
+    hipError_t e = hipSuccess;
+    if (ns) e = launch_shd_fold(ctx->stream, D.txs, dstx, (int)ns, ddesc, (int)nd, dcodes, drjok, dpst, dedst, dbst, ddst,
+                                dres, dindex, dres + ns);
+    if (e == hipSuccess)
+      e = launch_shp_fold(ctx->stream, D.txs, dptx, (int)np, dpgst, dedst, dpdst, dpres, dpindex, dpres + np);
+    return e;
   }));
-  // one download: the parts from the descriptions' statuses to the indices lie one after another in the arena
+  // one download per plan: the parts from the descriptions' statuses to the indices lie one after another in the arena
   const size_t res_bytes = Carve::span(2 * ns, 4) + sizeof(uint32_t) * ns, dst_span = Carve::span(nd, 256);
-  std::vector<uint8_t> back(dst_span + res_bytes), hh(hashes ? 32 * ns : 0);
+  std::vector<uint8_t> back(dst_span + res_bytes), hh(hashes ? 32 * nsh : 0), pback(np ? own[31] : 0);
   const uint8_t* const from = nd ? ddst : dres;
   const size_t skip = nd ? dst_span : 0;
-  HIPCHK(hipMemcpyAsync(back.data(), from, skip + res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (hashes) HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * ns, hipMemcpyDeviceToHost, ctx->stream));
+  if (ns) HIPCHK(hipMemcpyAsync(back.data(), from, skip + res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (np) HIPCHK(hipMemcpyAsync(pback.data(), dpdst, own[31], hipMemcpyDeviceToHost, ctx->stream));
+  if (hashes) HIPCHK(hipMemcpyAsync(hh.data(), D.hash, 32 * nsh, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(sig_sync(ctx));
   ctx->sig_ms += ms_before;
   const uint8_t* res = back.data() + skip;
@@ -710,8 +781,41 @@ extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, c
     status[t] = res[s], detail[t] = res[ns + s], index[t] = ix;
     if (hashes) memcpy(hashes + 32 * t, hh.data() + 32 * Q.stx[s].hash, 32);
   }
-  if (desc_status && nd) memcpy(desc_status, back.data(), nd);
+  const uint8_t* pres = pback.data() + Carve::span(npd, 256);
+  for (size_t q = 0; q < np; q++) {
+    const size_t t = R.ptx[q].tx;
+    uint32_t ix;
+    memcpy(&ix, pres + Carve::span(2 * np, 4) + 4 * q, 4);
+    status[t] = pres[q], detail[t] = pres[np + q], index[t] = ix;
+    if (hashes) memcpy(hashes + 32 * t, hh.data() + 32 * R.ptx[q].hash, 32);
+  }
+  if (desc_status && nd && !np) memcpy(desc_status, back.data(), nd);
+  if (desc_status && np) {  // both plans: each transaction's descriptions to their place in the window's order
+    for (size_t s = 0; s < ns; s++) {
+      const size_t t = Q.stx[s].tx;
+      memcpy(desc_status + desc_off[t], back.data() + Q.stx[s].desc0, (size_t)(desc_off[t + 1] - desc_off[t]));
+    }
+    for (size_t q = 0; q < np; q++) {
+      const size_t t = R.ptx[q].tx;
+      memcpy(desc_status + desc_off[t], pback.data() + R.ptx[q].desc0, (size_t)(desc_off[t + 1] - desc_off[t]));
+    }
+  }
   return ZG_OK;
+}
+
+extern "C" int zg_shielded_verify(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                                  const uint32_t* tx_branch_id, uint8_t* tx_status, uint8_t* status, uint64_t* index,
+                                  uint8_t* detail, uint8_t* hashes, uint64_t* desc_off, uint8_t* desc_status) {
+  return shielded_verify(ctx, ntx, txs, tx_off, tx_branch_id, 0, tx_status, status, index, detail, hashes, desc_off,
+                         desc_status);
+}
+
+extern "C" int zg_shielded_verify_flags(zg_ctx* ctx, size_t ntx, const uint8_t* txs, const uint64_t* tx_off,
+                                        const uint32_t* tx_branch_id, uint32_t flags, uint8_t* tx_status,
+                                        uint8_t* status, uint64_t* index, uint8_t* detail, uint8_t* hashes,
+                                        uint64_t* desc_off, uint8_t* desc_status) {
+  return shielded_verify(ctx, ntx, txs, tx_off, tx_branch_id, flags, tx_status, status, index, detail, hashes, desc_off,
+                         desc_status);
 }
 
 // ------------------------------------------------------------------ block bodies (zg_blocks.h)
@@ -1174,6 +1278,20 @@ extern "C" int zg_pghr13_vk_load_builtin(zg_ctx* ctx) {
   return zg_pghr13_vk_load_json(ctx, ZG_PGHR13_VK_JSON, strlen(ZG_PGHR13_VK_JSON));
 }
 
+// the equality weights rho_2..rho_5 and rho_1 of n proofs (16 bytes each, zg_pghr13.hip ZG_PGHR_RHO_BYTES):
+// seeded contexts (tests) derive them, others take them from the OS. -> false: getrandom failed
+static bool pghr13_rho(zg_ctx* ctx, size_t n, std::vector<uint8_t>& rho) {
+  rho.resize(80 * n);
+  if (!ctx->seeded) return os_random(rho.data(), rho.size());
+  for (size_t i = 0; i < n; i++) {
+    uint8_t h1[64];
+    seeded_bytes("zg-pghr13-rho", ctx->seed, i, &rho[80 * i], 64);
+    seeded_bytes("zg-pghr13-rho1", ctx->seed, i, h1, 64);
+    memcpy(&rho[80 * i + 64], h1, 16);
+  }
+  return true;
+}
+
 extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, const uint8_t* inputs,
                                 const uint8_t* n_inputs, uint8_t* status, float* kernel_ms) {
   if (!ctx || (n && (!proofs || !inputs || !status)) || n > (1u << 24)) return ZG_E_INVAL;
@@ -1187,19 +1305,8 @@ extern "C" int zg_pghr13_verify(zg_ctx* ctx, size_t n, const uint8_t* proofs, co
   }
   HIPCHK(hipSetDevice(ctx->device));
   if (!n) return ZG_OK;
-  // the equality weights rho_2..rho_5 and rho_1 (16 bytes each, zg_pghr13.hip ZG_PGHR_RHO_BYTES):
-  // seeded contexts (tests) derive them, others take them from the OS
-  std::vector<uint8_t> rho(80 * n);
-  if (ctx->seeded) {
-    for (size_t i = 0; i < n; i++) {
-      uint8_t h1[64];
-      seeded_bytes("zg-pghr13-rho", ctx->seed, i, &rho[80 * i], 64);
-      seeded_bytes("zg-pghr13-rho1", ctx->seed, i, h1, 64);
-      memcpy(&rho[80 * i + 64], h1, 16);
-    }
-  } else if (!os_random(rho.data(), rho.size())) {
-    return fail(ctx, ZG_E_INVAL, "getrandom failed");
-  }
+  std::vector<uint8_t> rho;
+  if (!pghr13_rho(ctx, n, rho)) return fail(ctx, ZG_E_INVAL, "getrandom failed");
   // one batch check per chunk of at most ctx->pghr_chunk proofs: the call's arena (~27 KB per proof,
   // mostly the b lines) stays bounded at the chunk size however large the caller's window is
   if (kernel_ms) *kernel_ms = 0;

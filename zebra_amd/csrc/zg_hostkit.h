@@ -190,7 +190,8 @@ void bn_key_release(BnDev* d, const BnKey* k);
 void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* halves, int* p7_side);
 int bn_pghr13_verify(const BnKey* k, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
                      const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
-                     uint8_t* status, float* kernel_ms, bool* batch_failed, DevArena& arena, std::string* err);
+                     uint8_t* status, float* kernel_ms, bool* batch_failed, DevArena& arena, std::string* err,
+                     bool on_device = false);  // on_device: proofs, inputs, ninputs, status are device buffers
 int bn_pairing(hipStream_t st, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt, std::string* err);
 
 }  // namespace zg

@@ -1068,9 +1068,13 @@ void bn_pghr13_shape(size_t n, int forced_b, int forced_k, int* B, int* K, int* 
   *p7_side = n >= 32768;
 }
 
+// on_device: proofs, inputs, ninputs and status are device buffers (rows another kernel gathered, statuses another
+// kernel reads): the pipeline runs over them where they are, nothing of them is copied, and the statuses are final
+// once the stream reaches what the caller enqueues next. rho is the host's either way.
 int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n, int forced_b, int forced_k,
                      const uint8_t* proofs, const uint8_t* inputs, const uint8_t* ninputs, const uint8_t* rho,
-                     uint8_t* status, float* kernel_ms, bool* batch_failed, DevArena& arena, std::string* err) {
+                     uint8_t* status, float* kernel_ms, bool* batch_failed, DevArena& arena, std::string* err,
+                     bool on_device) {
   if (batch_failed) *batch_failed = false;
   if (!n) return ZG_OK;
   int B, K, halves, p7_on_side;
@@ -1090,11 +1094,11 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   BLine* dbl;
   Bq12 *df, *dw, *dbseg, *dbtmp, *dseg, *dbw;
   const Part parts[] = {
-      {(void**)&dp, 296 * n},
-      {(void**)&din, 9 * 32 * n},
+      {(void**)&dp, on_device ? 0 : 296 * n},
+      {(void**)&din, on_device ? 0 : 9 * 32 * n},
       {(void**)&drho, ZG_PGHR_RHO_BYTES * n},
-      {(void**)&dst, n},
-      {(void**)&dni, ninputs ? n : 0},
+      {(void**)&dst, on_device ? 0 : n},
+      {(void**)&dni, ninputs && !on_device ? n : 0},
       {(void**)&dpts, sizeof(PghrPts) * n},
       {(void**)&ddec, sizeof(PghrDec) * n},
       {(void**)&dmul, sizeof(BA1) * ZG_PGHR_NMUL * n},
@@ -1116,6 +1120,8 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   for (const Part& q : parts) need += Carve::span(q.b, 256);
   HIPCHK_TO(err, arena.reserve(need, st));
   for (const Part& q : parts) *q.p = arena.carve<char>(q.b, 256);
+  if (on_device)
+    dp = const_cast<uint8_t*>(proofs), din = const_cast<uint8_t*>(inputs), dni = const_cast<uint8_t*>(ninputs), dst = status;
   struct Events {
     hipEvent_t e[8] = {};
     ~Events() {
@@ -1125,10 +1131,12 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
   } ev;
   hipEvent_t &e0 = ev.e[0], &e1 = ev.e[1], &g2fork = ev.e[4], &g2join = ev.e[5], &g2dec = ev.e[6], &stready = ev.e[7];
   for (hipEvent_t* x : {&g2fork, &g2join, &g2dec, &stready}) HIPCHK_TO(err, hipEventCreateWithFlags(x, hipEventDisableTiming));
-  HIPCHK_TO(err, hipMemcpyAsync(dp, proofs, 296 * n, hipMemcpyHostToDevice, st));
-  HIPCHK_TO(err, hipMemcpyAsync(din, inputs, 9 * 32 * n, hipMemcpyHostToDevice, st));
+  if (!on_device) {
+    HIPCHK_TO(err, hipMemcpyAsync(dp, proofs, 296 * n, hipMemcpyHostToDevice, st));
+    HIPCHK_TO(err, hipMemcpyAsync(din, inputs, 9 * 32 * n, hipMemcpyHostToDevice, st));
+  }
   HIPCHK_TO(err, hipMemcpyAsync(drho, rho, ZG_PGHR_RHO_BYTES * n, hipMemcpyHostToDevice, st));
-  if (ninputs) HIPCHK_TO(err, hipMemcpyAsync(dni, ninputs, n, hipMemcpyHostToDevice, st));
+  if (ninputs && !on_device) HIPCHK_TO(err, hipMemcpyAsync(dni, ninputs, n, hipMemcpyHostToDevice, st));
   if (kernel_ms) {
     HIPCHK_TO(err, hipEventCreate(&e0));
     HIPCHK_TO(err, hipEventCreate(&e1));
@@ -1232,8 +1240,8 @@ int bn_pghr13_verify(const BnKey* d, hipStream_t st, hipStream_t side, size_t n,
     HIPCHK_TO(err, hipGetLastError());
   }
   if (kernel_ms) HIPCHK_TO(err, hipEventRecord(e1, st));
-  HIPCHK_TO(err, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
-  HIPCHK_TO(err, hipStreamSynchronize(st));
+  if (!on_device) HIPCHK_TO(err, hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
+  if (!on_device || kernel_ms) HIPCHK_TO(err, hipStreamSynchronize(st));
   if (kernel_ms) HIPCHK_TO(err, hipEventElapsedTime(kernel_ms, e0, e1));
   return ZG_OK;
 }

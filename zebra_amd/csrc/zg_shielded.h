@@ -8,6 +8,9 @@
 // spends, outputs, transaction after transaction; description d is row d of the Groth16 batch. The RedJubjub rows
 // are the spends' spend_auth_sig checks and one binding_sig check per v4 transaction; the Ed25519 rows one per
 // transaction with JoinSplits. Every offset a lane follows comes from a TxLayout that tx_parse validated.
+// With ZG_SHIELDED_PHGR (row f18) the v2 / v3 transactions with JoinSplits are planned too, in records of their own
+// (ShpTx, ShpDesc, below the v4 routines): their descriptions are the rows of the PGHR13 pipeline, numbered apart
+// from the Groth16 rows, and their Ed25519 rows follow the v4 transactions'. Nothing of the v4 plan changes.
 #pragma once
 #include <vector>
 
@@ -24,6 +27,9 @@ constexpr uint32_t SHD_OK = 0, SHD_SPEND_AUTH_SIG = 9, SHD_PROOF_INVALID = 10, S
                    SHD_PROOF_FAILED = 12, SHD_BALANCE_VALUE = 13, SHD_BINDING_SIGNATURE = 14,
                    SHD_JOINSPLIT_ENCODING = 15, SHD_JOINSPLIT_PROOF = 16, SHD_ED_BASE = 16;  // + ZG_ED_* (1..3)
 constexpr uint32_t SHD_KIND_SPEND = 0, SHD_KIND_OUTPUT = 1, SHD_KIND_JOINSPLIT = 2;  // ZG_KIND_*, ZG_PREP_KIND_*
+constexpr uint32_t SHD_KIND_JOINSPLIT_BN = 3;                                        // ZG_PREP_KIND_JOINSPLIT_BN
+constexpr uint32_t SHD_JOINSPLIT_PGHR_PROOF = 20, SHD_PHGR = 1;                      // ZG_SHD_*, ZG_SHIELDED_PHGR
+constexpr uint32_t SHD_PHGR_JS_BYTES = 1802, SHD_PHGR_PROOF_BYTES = 296;
 constexpr uint32_t SHD_NO_ROW = 0xffffffffu;
 constexpr uint32_t SHD_JS_BYTES = 1698, SHD_SPEND_BYTES = 384, SHD_OUTPUT_BYTES = 948, SHD_FIELD_BYTES = 304;
 constexpr uint32_t SHD_ST_DECODE_INVALID = 1, SHD_ST_MALFORMED_VK = 2, SHD_ST_VERIFY_FAILED = 3;  // ZG_STATUS_*
@@ -193,6 +199,108 @@ inline bool shd_plan(const std::vector<ShDevTx>& dtx, size_t ntx, const uint8_t*
   }
   for (ShdTx& S : P.stx) S.rj = P.nrj++;  // the binding rows follow the spends'
   return true;
+}
+
+// ------------------------------------------------------------------ PHGR JoinSplits (ZG_SHIELDED_PHGR, row f18)
+// What JoinSplitVerification::check and JoinSplitProof::check run for a transaction before v4
+// (accept_transaction.rs:575-596,649-657; sprout.rs:34-68, the PHGR branch; crypto/src/pghr13.rs:69-105): the Ed25519
+// signature over the no-input hash, then Pghr13Proof::from_raw and verify per description. Such a transaction has no
+// Sapling part: no binding row, no value commitments, no RedJubjub rows.
+struct ShpDesc {
+  uint32_t stx;  // its ShpTx
+  uint32_t idx;  // its place among the transaction's JoinSplits; its row in the PGHR13 rows is its own number
+};
+struct ShpTx {
+  uint32_t tx;     // its ShDevTx
+  uint32_t desc0;  // its first description (PHGR numbering)
+  uint32_t hash;   // the row of its no-input signature hash
+  uint32_t ed;     // its Ed25519 row
+};
+
+// PHGR description `row`: its 296-byte proof and its nine BN254 inputs, 253 bits each (Input::into_bn_frs), from the
+// fields where they lie; the descriptions of a transaction are L.js_size bytes apart
+ZG_SH_HD void shp_gather(const uint8_t* arena, const ShDevTx* txs, const ShpTx* ptx, const ShpDesc& d, size_t row,
+                         uint8_t* proofs, uint8_t* inputs) {
+  const ShDevTx& T = txs[ptx[d.stx].tx];
+  const uint8_t* p = arena + T.base + T.L.js_off + (size_t)T.L.js_size * d.idx;
+  prep_joinsplit_bits(p + 16, p + 208, p + 48, p + 80, p + 240, p + 272, p + 112, p + 144, p, p + 8,
+                      arena + T.base + T.L.jspub_off, 253, inputs + 288 * row);
+  shd_copy(proofs + (size_t)SHD_PHGR_PROOF_BYTES * row, p + 304, (int)SHD_PHGR_PROOF_BYTES);
+}
+
+// after the signature hashes: the transaction's Ed25519 row over its hash
+ZG_SH_HD void shp_tx_rows(const uint8_t* arena, const ShDevTx* txs, const ShpTx& S, const uint8_t* hashes,
+                          uint8_t* ed_pk, uint8_t* ed_sig, uint8_t* ed_msg) {
+  const ShDevTx& T = txs[S.tx];
+  const uint8_t* pub = arena + T.base + T.L.jspub_off;
+  shd_copy(ed_pk + (size_t)32 * S.ed, pub, 32);
+  shd_copy(ed_sig + (size_t)64 * S.ed, pub + 32, 64);
+  shd_copy(ed_msg + (size_t)32 * S.ed, hashes + (size_t)32 * S.hash, 32);
+}
+
+// sprout::verify's class from the PGHR13 status: from_raw fails -> InvalidEncoding, verify false -> InvalidPGHRProof.
+// ZG_STATUS_INPUT_NONCANONICAL cannot occur (a 253-bit chunk is below r); it would count as the proof's failure
+ZG_SH_HD uint32_t shp_desc_status(uint32_t proof) {
+  return proof == 0 ? SHD_OK : proof == SHD_ST_DECODE_INVALID ? SHD_JOINSPLIT_ENCODING : SHD_JOINSPLIT_PGHR_PROOF;
+}
+
+// The reference's first error of a transaction before v4: the Ed25519 signature, then the JoinSplits in order; there
+// the fold stops (no balance value, no binding signature). Writes the classes of its n_js descriptions as it goes.
+ZG_SH_HD uint32_t shp_tx_fold(const TxLayout& L, const ShpTx& S, const uint8_t* proof_status, const uint8_t* ed,
+                              uint8_t* desc_status, uint32_t* index, uint32_t* detail) {
+  uint32_t st = SHTX_OK;
+  *index = 0, *detail = SHD_OK;
+  if (ed[S.ed]) {
+    *detail = SHD_ED_BASE + ed[S.ed];
+    st = SHTX_JOINSPLIT_SIGNATURE;
+  }
+  for (uint32_t j = 0; j < L.n_js; j++) {
+    const uint32_t c = shp_desc_status(proof_status[S.desc0 + j]);
+    desc_status[S.desc0 + j] = (uint8_t)c;
+    if (c && st == SHTX_OK) {
+      *detail = c, *index = j;
+      st = SHTX_INVALID_JOINSPLIT;
+    }
+  }
+  return st;
+}
+
+struct ShpPlan {
+  std::vector<ShpTx> ptx;
+  std::vector<ShpDesc> desc;
+};
+
+// After shd_plan: every transaction it left SHTX_HOST (before v4, with JoinSplits) is planned, OK until the fold says
+// otherwise; its Ed25519 row follows the ned rows of the v4 plan. -> false: more than 2^30 descriptions with the
+// nd of the v4 plan
+inline bool shp_plan(const std::vector<ShDevTx>& dtx, size_t ntx, size_t nd, uint32_t ned, uint8_t* status, ShpPlan& R) {
+  for (size_t t = 0; t < ntx; t++) {
+    if (status[t] != SHTX_HOST) continue;
+    const TxLayout& L = dtx[t].L;
+    if (nd + R.desc.size() + (uint64_t)L.n_js > (1u << 30)) return false;
+    const uint32_t s = (uint32_t)R.ptx.size();
+    R.ptx.push_back(ShpTx{(uint32_t)t, (uint32_t)R.desc.size(), 0, ned + s});
+    for (uint32_t j = 0; j < L.n_js; j++) R.desc.push_back(ShpDesc{s, j});
+    status[t] = SHTX_OK;
+  }
+  return true;
+}
+
+// desc_off of the window, both plans: the descriptions of transaction t, v4 or before, follow those of t - 1
+inline void shd_desc_offsets(const ShdPlan& Q, const ShpPlan& R, size_t ntx, uint64_t* desc_off) {
+  const size_t ns = Q.stx.size(), np = R.ptx.size();
+  desc_off[0] = 0;
+  for (size_t t = 0, s = 0, q = 0; t < ntx; t++) {
+    uint64_t n = 0;
+    if (s < ns && Q.stx[s].tx == t) {
+      n = (s + 1 < ns ? Q.stx[s + 1].desc0 : Q.desc.size()) - Q.stx[s].desc0;
+      s++;
+    } else if (q < np && R.ptx[q].tx == t) {
+      n = (q + 1 < np ? R.ptx[q + 1].desc0 : R.desc.size()) - R.ptx[q].desc0;
+      q++;
+    }
+    desc_off[t + 1] = desc_off[t] + n;
+  }
 }
 
 }  // namespace zg

@@ -37,6 +37,8 @@ INPUT_ERRORS = {INPUT_EQUALVERIFY: "EqualVerify", INPUT_SIGNATURE_DER: "Signatur
 # and ZG_SHD_* (the inner error class; a description's own first failing class)
 (SHTX_OK, SHTX_NONE, SHTX_JOINSPLIT_SIGNATURE, SHTX_INVALID_JOINSPLIT, SHTX_INVALID_SAPLING, SHTX_HOST,
  SHTX_TX_MALFORMED, SHTX_TX_NONCANONICAL) = range(8)
+SHD_JOINSPLIT_PGHR_PROOF = 20   # ErrorKind::InvalidPGHRProof: a PHGR description under SHIELDED_PHGR
+SHIELDED_PHGR = 1               # zg_shielded_verify_flags: v2 / v3 transactions with JoinSplits are checked in the call
 SHTX_ERRORS = {SHTX_JOINSPLIT_SIGNATURE: "JoinSplitSignature", SHTX_INVALID_JOINSPLIT: "InvalidJoinSplit",
                SHTX_INVALID_SAPLING: "InvalidSapling"}
 (SHD_OK, SHD_VALUE_COMMITMENT_INVALID, SHD_VALUE_COMMITMENT_SMALL_ORDER, SHD_ANCHOR, SHD_RANDOMIZED_KEY_INVALID,
@@ -131,6 +133,8 @@ def lib():
         L.zg_inputs_verify.argtypes = [vp, sz, u8p, u64p, u32p, sz, u32p, u32p, u8p, u32p, u64p, ctypes.c_uint32, u8p,
                                        u8p, u8p, u8p]
         L.zg_shielded_verify.argtypes = [vp, sz, u8p, u64p, u32p, u8p, u8p, u64p, u8p, u8p, u64p, u8p]
+        L.zg_shielded_verify_flags.argtypes = [vp, sz, u8p, u64p, u32p, ctypes.c_uint32, u8p, u8p, u64p, u8p, u8p, u64p,
+                                               u8p]
         L.zg_block_layout.argtypes = [u8p, sz, u64p, u64p, sz]
         L.zg_txids.argtypes = [vp, sz, u8p, u64p, u8p]
         L.zg_blocks_verify.argtypes = [vp, sz, u8p, u64p, ctypes.c_uint64, ctypes.c_uint64, sz, u8p, u8p, u64p, u8p,
@@ -655,13 +659,19 @@ class Context:
         return (list(ts.raw[:ntx]), list(st.raw[:n]), list(dt.raw[:n]) if want_detail else None,
                 [hs.raw[32 * i:32 * i + 32] for i in range(n)] if want_hashes else None)
 
-    def shielded_verify(self, txs, branch_ids, want_hashes=True, want_desc=True):
+    def shielded_verify(self, txs, branch_ids, want_hashes=True, want_desc=True, phgr=False, flags=None):
         """JoinSplitVerification::check and SaplingProof::check (verification/src/accept_transaction.rs:575-596,
         649-657,707-714) of every transaction of a window from its serialized bytes, ONE call -> (TX_* per transaction,
         SHTX_* per transaction: the reference's first error, the failing description's index in its list, the SHD_*
         inner class, the 32-byte no-input signature hash of a v4 transaction (zero otherwise) or None, per
         transaction the list of its descriptions' own SHD_* classes (JoinSplits, spends, outputs) or None).
-        SHTX_HOST: PHGR JoinSplits, the caller keeps pghr13_verify and ed25519_verify for it"""
+        SHTX_HOST: PHGR JoinSplits, the caller keeps pghr13_verify and ed25519_verify for it. phgr=True
+        (SHIELDED_PHGR, zg_shielded_verify_flags): those transactions are checked in the call as well, the Ed25519
+        signature, then Pghr13Proof::from_raw and verify per description (SHD_JOINSPLIT_ENCODING,
+        SHD_JOINSPLIT_PGHR_PROOF), with their hashes and descriptions returned as a v4 transaction's. flags: the raw
+        flag word instead"""
+        if flags is None:
+            flags = SHIELDED_PHGR if phgr else 0
         ntx = len(txs)
         arena, tx_off, branch = pack_shielded(txs, branch_ids)
         ts = ctypes.create_string_buffer(max(ntx, 1))
@@ -672,7 +682,11 @@ class Context:
         doff = (ctypes.c_uint64 * (ntx + 1))() if want_desc else None
         # a description takes at least 384 bytes of its transaction
         ds = ctypes.create_string_buffer(len(arena) // 384 + 1) if want_desc else None
-        self._chk(lib().zg_shielded_verify(self._p, ntx, arena + b"\0", tx_off, branch, ts, st, ix, dt, hs, doff, ds))
+        if flags:
+            self._chk(lib().zg_shielded_verify_flags(self._p, ntx, arena + b"\0", tx_off, branch, flags, ts, st, ix, dt, hs,
+                                                     doff, ds))
+        else:
+            self._chk(lib().zg_shielded_verify(self._p, ntx, arena + b"\0", tx_off, branch, ts, st, ix, dt, hs, doff, ds))
         return (list(ts.raw[:ntx]), list(st.raw[:ntx]), list(ix[:ntx]), list(dt.raw[:ntx]),
                 [hs.raw[32 * i:32 * i + 32] for i in range(ntx)] if want_hashes else None,
                 [list(ds.raw[doff[t]:doff[t + 1]]) for t in range(ntx)] if want_desc else None)
